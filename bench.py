@@ -14,12 +14,23 @@ breast-cancer scale N=11165 genes, H=40, 256 trajectory intervals per GPU, dopri
 `--gpus N` with N > 1 and no RANK in the environment: this process starts N ranks itself (torch.distributed.run as a
 child, one rank per device, before anything touches a GPU) and exits with the child's code; rank 0 prints the line.
 Scaling: N = 1 and `--scaling weak` (default): every rank integrates its own 256 trajectories (no data-path collective).
-With N > 1 the default also measures BASELINE.json config 4 as written -- "256 trajectory batch sharded 1/2/4/8" --
+With N > 1, `--full` also measures BASELINE.json config 4 as written -- "256 trajectory batch sharded 1/2/4/8" --
 in the same run: `extra.strong` holds the step time / rate of the ONE 256-trajectory batch sharded over the ranks (loss
 normalised by the GLOBAL batch); `--scaling strong` makes that the headline instead.
 
 Metric: gene x trajectory RHS evaluations per second = sum over samples of (forward NFE + augmented NFE) * N / time.
 Prints ONE JSON line (rank 0).
+
+A plain run does what the headline needs and nothing else: set-up, the untimed pre-warm and the `--warmup` steps, exactly
+`--steps` timed steps, one statistics solve for the evaluation count, the line.  `--full` adds everything else the bench
+measures: five more timed windows, per-kernel launch times and the roofline, the reference's training step, the sharded
+(strong-scaling) and reference-batch-size steps, and the CPU baselines (`--no-extras` / `--no-cpu-baseline` trim those).
+
+`--dump-outputs DIR`: after the timed steps, what the LAST timed step computed -- the solution and the gradients a caller
+of the step receives (dL/dy0 and the six parameter gradients, in the reference's layouts) -- as float32 `DIR/<name>.npy`
+(rank 0).  The inputs are seeded, so two builds run with the same arguments can be compared file for file.  Above 64 MB
+in all, every array is cut to the same fraction of its elements: a flat vector of the elements at sorted positions drawn
+without replacement by `numpy.random.default_rng(0)`.  Dumps inside the tree go under `bench_outputs/` (kept out of git).
 """
 import argparse
 import json
@@ -50,7 +61,11 @@ def make_problem(wl, device, seed):
     import phoenix_amd
     N, H, B = wl["N"], wl["H"], wl["B"]
     g = torch.Generator(device="cpu").manual_seed(seed)
-    net = phoenix_amd.ODENet("cpu", N, neurons=H)
+    # the constructor's own draws (biases, the sparse init) come from the global generator: seeded here, so that the
+    # inputs are the same from run to run, without changing the caller's random state
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        net = phoenix_amd.ODENet("cpu", N, neurons=H)
     with torch.no_grad():
         if wl.get("init", "dense") == "dense":
             # trained-like dense factors (Adam densifies the 95%-sparse init), SURVEY 8d
@@ -68,7 +83,8 @@ def make_problem(wl, device, seed):
     return net, y0.to(device), t.to(device)
 
 
-def one_step(net, y0, t, G, method, world):
+def one_step(net, y0, t, G, method, world, keep=None):
+    """`keep`: a dict that receives this step's solution (detached) and its y0 leaf (whose .grad is dL/dy0)"""
     import phoenix_amd
     from phoenix_amd import parallel
     for p in net.parameters():
@@ -82,7 +98,30 @@ def one_step(net, y0, t, G, method, world):
     torch.autograd.backward(sol, G)          # G = dL/dsol [T,B,1,N]: the backward solve is entered with it as it is
     if world > 1:
         parallel.allreduce_grads(net)
+    if keep is not None:
+        keep["sol"], keep["y0"] = sol.detach(), y
     return sol
+
+
+DUMP_BYTES = 63 * 10 ** 6   # float32 payload of --dump-outputs; the .npy headers stay within 64 MB with it
+
+
+def dump_outputs(dirname, sol, y0_leaf, net):
+    """--dump-outputs: the solution, dL/dy0 and the parameter gradients of one step as float32 .npy files; above the
+    budget every array keeps the same fraction of its elements at seeded positions (module docstring)"""
+    arrays = {"solution": sol, "grad_y0": y0_leaf.grad}
+    for name, p in net.named_parameters():
+        arrays["grad_" + name.replace(".", "_")] = p.grad
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size * 4 for a in arrays.values())
+    frac = min(1.0, DUMP_BYTES / total)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            flat = a.reshape(-1)
+            idx = np.sort(np.random.default_rng(0).choice(flat.size, int(flat.size * frac), replace=False))
+            a = flat[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline_batched(wl, net, y0, t, G):
@@ -240,13 +279,19 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="breast", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: more timed windows, per-kernel launch times + roofline, the "
+                         "training step, sharded and reference-batch steps, CPU baselines (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (solution, dL/dy0, parameter gradients) as float32 "
+                         "DIR/<name>.npy, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="profiling runs: only the timed loop and the per-kernel timing (no training step, no "
+                    help="with --full, profiling runs: only the timed loop and the per-kernel timing (no training step, no "
                          "strong-scaling shards: their launches would be averaged into the per-kernel profile)")
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
-                    help="default: weak is the headline; with more than one rank the sharded (strong) problem is "
-                         "measured in the same run and reported under extra.strong")
+                    help="default: weak is the headline; with more than one rank and --full the sharded (strong) problem "
+                         "is measured in the same run and reported under extra.strong")
     ap.add_argument("--status", default="deferred", choices=["deferred", "immediate"],
                     help="solver status read-back: behind the backward kernel (checked at a later engine call; the "
                          "library default) or a blocking round trip at the end of every backward()")
@@ -259,7 +304,10 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = PLUMBING TEST ONLY (CPU, tests/test_bench_cpu.py): rank spawning, barriers, the gradient "
                          "all-reduce and the output line with a stub in place of the engine; prints value null")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -396,8 +444,10 @@ def main(args):
             dist.barrier()
         torch.cuda.synchronize()
 
+    last = {}
+
     def step():
-        one_step(net, y0, t, G, wl["method"], wdist)
+        one_step(net, y0, t, G, wl["method"], wdist, keep=last)
 
     # Untimed device pre-warm.  A fresh process on an idle GPU starts at low clocks with cold caches, lazily created RCCL
     # communicators and a growing caching allocator, and a 20-step timed region is ~20 ms: the pre-warm runs the same
@@ -415,38 +465,42 @@ def main(args):
     for _ in range(args.warmup):
         step()
     elapsed = timed_region(step, sync_all, args.steps, engine, use_dist, device)
-    # the same region five more times: how far single windows of K steps scatter on this box (p50 / p90)
-    windows = [elapsed / args.steps * 1e3]
-    for _ in range(5):
-        windows.append(timed_region(step, sync_all, args.steps, engine, use_dist, device) / args.steps * 1e3)
-
-    # ---- per-kernel timing with HIP events on the launch stream + NFE accounting (rank-local).
-    # The library records one event pair immediately around each solve kernel, on the stream it is launched on
-    # (phx_debug_queue_kernel_events: a FIFO, one pair per solve launch, forward and backward alternating), while the
-    # SAME steps as in the timed region run back to back -- the launch durations are those of the steady state the
-    # headline is measured in (an isolated launch behind a synchronize runs ~4 % longer: cold caches), and they are what
-    # `rocprofv3 --kernel-trace --stats` of this command averages.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["sol"], last["y0"], net)
     from phoenix_amd import _lib
-    import ctypes as C
-    nrep = max(5, min(args.steps, 20))
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(nrep)]
-    for quad in ev:
-        for e in quad:
-            e.record()   # instantiates the underlying hipEvent_t
-    torch.cuda.synchronize()
-    for _ in range(3):
-        step()
-    for quad in ev:
-        _lib.load().phx_debug_queue_kernel_events(C.c_void_p(quad[0].cuda_event), C.c_void_p(quad[1].cuda_event))
-        _lib.load().phx_debug_queue_kernel_events(C.c_void_p(quad[2].cuda_event), C.c_void_p(quad[3].cuda_event))
-    for _ in range(nrep):
-        step()
-    engine.check_pending_status(wait=True)
-    torch.cuda.synchronize()
-    _lib.load().phx_debug_queue_kernel_events(None, None)
-    fwd_ms = [q[0].elapsed_time(q[1]) for q in ev]
-    adj_ms = [q[2].elapsed_time(q[3]) for q in ev]
-    fwd_ms_avg, adj_ms_avg = float(np.mean(fwd_ms)), float(np.mean(adj_ms))
+
+    if args.full:
+        # the same region five more times: how far single windows of K steps scatter on this box (p50 / p90)
+        windows = [elapsed / args.steps * 1e3]
+        for _ in range(5):
+            windows.append(timed_region(step, sync_all, args.steps, engine, use_dist, device) / args.steps * 1e3)
+
+        # ---- per-kernel timing with HIP events on the launch stream (rank-local).
+        # The library records one event pair immediately around each solve kernel, on the stream it is launched on
+        # (phx_debug_queue_kernel_events: a FIFO, one pair per solve launch, forward and backward alternating), while the
+        # SAME steps as in the timed region run back to back -- the launch durations are those of the steady state the
+        # headline is measured in (an isolated launch behind a synchronize runs ~4 % longer: cold caches), and they are
+        # what `rocprofv3 --kernel-trace --stats` of this command averages.
+        import ctypes as C
+        nrep = max(5, min(args.steps, 20))
+        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(nrep)]
+        for quad in ev:
+            for e in quad:
+                e.record()   # instantiates the underlying hipEvent_t
+        torch.cuda.synchronize()
+        for _ in range(3):
+            step()
+        for quad in ev:
+            _lib.load().phx_debug_queue_kernel_events(C.c_void_p(quad[0].cuda_event), C.c_void_p(quad[1].cuda_event))
+            _lib.load().phx_debug_queue_kernel_events(C.c_void_p(quad[2].cuda_event), C.c_void_p(quad[3].cuda_event))
+        for _ in range(nrep):
+            step()
+        engine.check_pending_status(wait=True)
+        torch.cuda.synchronize()
+        _lib.load().phx_debug_queue_kernel_events(None, None)
+        fwd_ms = [q[0].elapsed_time(q[1]) for q in ev]
+        adj_ms = [q[2].elapsed_time(q[3]) for q in ev]
+        fwd_ms_avg, adj_ms_avg = float(np.mean(fwd_ms)), float(np.mean(adj_ms))
     # NFE accounting: one more solve through the engine entry points (statistics outputs)
     engine.set_status_mode("immediate")
     p = engine.Params(net.net_sums.linear_out.weight, net.net_sums.linear_out.bias, net.net_prods.linear_out.weight,
@@ -477,7 +531,7 @@ def main(args):
 
     # ---- the other scaling mode in the same run (more than one rank, no explicit --scaling): config 4 as written
     other = None
-    if world > 1 and args.scaling is None and not args.no_extras:
+    if args.full and world > 1 and args.scaling is None and not args.no_extras:
         engine.set_status_mode(args.status)
         net2, y02, t2, G2, B2, _ = problem("strong")
 
@@ -512,76 +566,76 @@ def main(args):
 
     if rank == 0:
         P = 4 * H * N + 2 * H + N
-        # ALGORITHMIC bytes: per RHS eval of a batch of B: 4P + 8BN; per augmented eval: 2*4P + 16BN.
-        # Units per launch = batch-evaluations = (sum_b nfe_b) / B.
-        alg_fwd = (nfe_fwd / B) * (4 * P + 8 * B * N)
-        alg_adj = (nfe_aug / B) * (8 * P + 16 * B * N)
-        # ALGORITHMIC flops: 8BNH per RHS eval of the batch, 24BNH per augmented eval (forward + VJP
-        # w.r.t. y + VJP w.r.t. the parameters).
-        flop_fwd = (nfe_fwd / B) * 8.0 * B * N * H
-        flop_adj = (nfe_aug / B) * 24.0 * B * N * H
-        mid = _lib.METHODS[wl["method"]]
-        adj_kernel = {0: "k_solve_adj", 1: "k1_solve_adj", 2: "k1_solve_adj2", 3: "k1_solve_adj3", 4: "k1_solve_adj3c"}[
-            _lib.load().phx_debug_adjoint_kernel_m(N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid)]
-        fwd_kernel = {0: "k_solve_fwd", 1: "k1_solve_fwd", 3: "k1_solve_fwd3", 4: "k1_solve_fwd3c"}[
-            _lib.load().phx_debug_forward_kernel_m(N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid)]
-        dom = adj_kernel if adj_ms_avg >= fwd_ms_avg else fwd_kernel   # key into the PMC summary
-        dom_launches = max(1, _lib.load().phx_debug_solve_launches(
-            _lib.OP_ADJOINT if dom == adj_kernel else _lib.OP_ODEINT, N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid))
-        alg, flop, ms = (alg_adj, flop_adj, adj_ms_avg) if dom == adj_kernel else (alg_fwd, flop_fwd, fwd_ms_avg)
-        achieved = alg / (ms * 1e-3) / 1e9
-        # Which roof binds: arithmetic intensity of the algorithmic figures against the fp32 ridge of the part
-        # (157.3 TFLOP/s f32-input MFMA / 8 TB/s HBM = 19.7 flop/B, MI355X_MICROARCH.md); SURVEY 8d: C4 at B = 256
-        # sits above it, the small-batch reference shapes below.
-        PEAK_HBM, PEAK_MFMA_F32 = 8000.0, 157.3
-        tflops = flop / (ms * 1e-3) / 1e12
-        mfma_bound = (flop / alg) > (PEAK_MFMA_F32 * 1e12) / (PEAK_HBM * 1e9)
-        # HBM traffic per launch from the committed PMC passes of this same command (rocprofv3 --pmc FETCH_SIZE /
-        # --pmc WRITE_SIZE, separate runs; FETCH_SIZE doubled per MI355X_MICROARCH.md for 16-B/lane streams)
-        # (the counters cannot be read while the bench runs un-profiled: the figure is the committed summary of the
-        # profiled run of this same command, regenerated by tools/collect_profiles.sh)
-        # Provenance: the summary names the library it was collected on (sha256 of libphoenix_hip.so, written by
-        # tools/summarize_profiles.py); a summary of ANOTHER build is not this run's traffic -> `traffic: null` + a note.
-        traffic, pmc_file, pmc_note = None, None, None
-        import hashlib
-        lib_sha = hashlib.sha256(open(_lib.lib_path(), "rb").read()).hexdigest()
-        for tag in ("r5", "r4", "r3", "r2"):
-            cand = os.path.join(ROOT, "profiles", "%s_%s_pmc_hbm.json" % (tag, args.workload))
-            if os.path.exists(cand):
-                try:
-                    pmc = json.load(open(cand))
-                    if pmc.get("library_sha256") != lib_sha:
-                        pmc_note = ("%s was collected on another build of libphoenix_hip.so (sha256 %s, running %s): traffic "
-                                    "not reported" % (os.path.basename(cand), str(pmc.get("library_sha256"))[:12], lib_sha[:12]))
+        if args.full:
+            # ALGORITHMIC bytes: per RHS eval of a batch of B: 4P + 8BN; per augmented eval: 2*4P + 16BN.
+            # Units per launch = batch-evaluations = (sum_b nfe_b) / B.
+            alg_fwd = (nfe_fwd / B) * (4 * P + 8 * B * N)
+            alg_adj = (nfe_aug / B) * (8 * P + 16 * B * N)
+            # ALGORITHMIC flops: 8BNH per RHS eval of the batch, 24BNH per augmented eval (forward + VJP
+            # w.r.t. y + VJP w.r.t. the parameters).
+            flop_fwd = (nfe_fwd / B) * 8.0 * B * N * H
+            flop_adj = (nfe_aug / B) * 24.0 * B * N * H
+            mid = _lib.METHODS[wl["method"]]
+            adj_kernel = {0: "k_solve_adj", 1: "k1_solve_adj", 2: "k1_solve_adj2", 3: "k1_solve_adj3", 4: "k1_solve_adj3c"}[
+                _lib.load().phx_debug_adjoint_kernel_m(N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid)]
+            fwd_kernel = {0: "k_solve_fwd", 1: "k1_solve_fwd", 3: "k1_solve_fwd3", 4: "k1_solve_fwd3c"}[
+                _lib.load().phx_debug_forward_kernel_m(N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid)]
+            dom = adj_kernel if adj_ms_avg >= fwd_ms_avg else fwd_kernel   # key into the PMC summary
+            dom_launches = max(1, _lib.load().phx_debug_solve_launches(
+                _lib.OP_ADJOINT if dom == adj_kernel else _lib.OP_ODEINT, N, H, B, T, _lib.CTRL_PER_TRAJECTORY, mid))
+            alg, flop, ms = (alg_adj, flop_adj, adj_ms_avg) if dom == adj_kernel else (alg_fwd, flop_fwd, fwd_ms_avg)
+            achieved = alg / (ms * 1e-3) / 1e9
+            # Which roof binds: arithmetic intensity of the algorithmic figures against the fp32 ridge of the part
+            # (157.3 TFLOP/s f32-input MFMA / 8 TB/s HBM = 19.7 flop/B, MI355X_MICROARCH.md); SURVEY 8d: C4 at B = 256
+            # sits above it, the small-batch reference shapes below.
+            PEAK_HBM, PEAK_MFMA_F32 = 8000.0, 157.3
+            tflops = flop / (ms * 1e-3) / 1e12
+            mfma_bound = (flop / alg) > (PEAK_MFMA_F32 * 1e12) / (PEAK_HBM * 1e9)
+            # HBM traffic per launch from the committed PMC passes of this same command (rocprofv3 --pmc FETCH_SIZE /
+            # --pmc WRITE_SIZE, separate runs; FETCH_SIZE doubled per MI355X_MICROARCH.md for 16-B/lane streams)
+            # (the counters cannot be read while the bench runs un-profiled: the figure is the committed summary of the
+            # profiled run of this same command, regenerated by tools/collect_profiles.sh)
+            # Provenance: the summary names the library it was collected on (sha256 of libphoenix_hip.so, written by
+            # tools/summarize_profiles.py); a summary of ANOTHER build is not this run's traffic -> `traffic: null` + a note.
+            traffic, pmc_file, pmc_note = None, None, None
+            import hashlib
+            lib_sha = hashlib.sha256(open(_lib.lib_path(), "rb").read()).hexdigest()
+            for tag in ("r5", "r4", "r3", "r2"):
+                cand = os.path.join(ROOT, "profiles", "%s_%s_pmc_hbm.json" % (tag, args.workload))
+                if os.path.exists(cand):
+                    try:
+                        pmc = json.load(open(cand))
+                        if pmc.get("library_sha256") != lib_sha:
+                            pmc_note = ("%s was collected on another build of libphoenix_hip.so (sha256 %s, running %s): traffic "
+                                        "not reported" % (os.path.basename(cand), str(pmc.get("library_sha256"))[:12], lib_sha[:12]))
+                            break
+                        # (per-launch counters x the launches one solve of this batch makes: 256 B-cell trajectories = two)
+                        traffic = (2.0 * pmc["FETCH_SIZE_KB_per_launch"][dom] + pmc["WRITE_SIZE_KB_per_launch"][dom]) * 1024.0 * dom_launches
+                        pmc_file = os.path.relpath(cand, ROOT)
                         break
-                    # (per-launch counters x the launches one solve of this batch makes: 256 B-cell trajectories = two)
-                    traffic = (2.0 * pmc["FETCH_SIZE_KB_per_launch"][dom] + pmc["WRITE_SIZE_KB_per_launch"][dom]) * 1024.0 * dom_launches
-                    pmc_file = os.path.relpath(cand, ROOT)
-                    break
-                except Exception as exc:   # noqa: BLE001
-                    traffic, pmc_note = None, "%s: %r" % (os.path.basename(cand), exc)
-                    break
-        roofline = {"bound": "mfma" if mfma_bound else "hbm", "kernel": dom,
-                    "achieved": tflops if mfma_bound else achieved,
-                    "peak": PEAK_MFMA_F32 if mfma_bound else PEAK_HBM,
-                    "unit": "TFLOP/s" if mfma_bound else "GB/s",
-                    "frac": tflops / PEAK_MFMA_F32 if mfma_bound else achieved / PEAK_HBM,
-                    "arithmetic_intensity_flop_per_byte": flop / alg,
-                    "hbm": {"achieved_GBps": achieved, "peak_GBps": PEAK_HBM, "frac": achieved / PEAK_HBM},
-                    "mfma_f32": {"achieved_TFLOPs": tflops, "peak_TFLOPs": PEAK_MFMA_F32,
-                                 "frac": tflops / PEAK_MFMA_F32, "algorithmic_flop_per_launch": flop},
-                    "traffic": traffic,
-                    "measured_hbm_GBps": (traffic / (ms * 1e-3) / 1e9) if traffic else None,
-                    "traffic_source": ("%s (2*FETCH_SIZE + WRITE_SIZE of a separate profiled run of this command on this "
-                                       "same library build, sha256 %s; not measured in this run)"
-                                       % (pmc_file, lib_sha[:12])) if traffic else pmc_note,
-                    "library_sha256": lib_sha,
-                    "algorithmic_bytes_per_launch": alg, "launch_ms": ms, "launches_per_solve": dom_launches,
-                    "forward": {"kernel": fwd_kernel, "launch_ms": fwd_ms_avg, "GBps": alg_fwd / (fwd_ms_avg * 1e-3) / 1e9,
-                                "TFLOPs": flop_fwd / (fwd_ms_avg * 1e-3) / 1e12, "batch_evals": nfe_fwd / B},
-                    "adjoint": {"kernel": adj_kernel, "launch_ms": adj_ms_avg, "GBps": alg_adj / (adj_ms_avg * 1e-3) / 1e9,
-                                "TFLOPs": flop_adj / (adj_ms_avg * 1e-3) / 1e12, "batch_evals": nfe_aug / B}}
-        ws = sorted(windows)
+                    except Exception as exc:   # noqa: BLE001
+                        traffic, pmc_note = None, "%s: %r" % (os.path.basename(cand), exc)
+                        break
+            roofline = {"bound": "mfma" if mfma_bound else "hbm", "kernel": dom,
+                        "achieved": tflops if mfma_bound else achieved,
+                        "peak": PEAK_MFMA_F32 if mfma_bound else PEAK_HBM,
+                        "unit": "TFLOP/s" if mfma_bound else "GB/s",
+                        "frac": tflops / PEAK_MFMA_F32 if mfma_bound else achieved / PEAK_HBM,
+                        "arithmetic_intensity_flop_per_byte": flop / alg,
+                        "hbm": {"achieved_GBps": achieved, "peak_GBps": PEAK_HBM, "frac": achieved / PEAK_HBM},
+                        "mfma_f32": {"achieved_TFLOPs": tflops, "peak_TFLOPs": PEAK_MFMA_F32,
+                                     "frac": tflops / PEAK_MFMA_F32, "algorithmic_flop_per_launch": flop},
+                        "traffic": traffic,
+                        "measured_hbm_GBps": (traffic / (ms * 1e-3) / 1e9) if traffic else None,
+                        "traffic_source": ("%s (2*FETCH_SIZE + WRITE_SIZE of a separate profiled run of this command on this "
+                                           "same library build, sha256 %s; not measured in this run)"
+                                           % (pmc_file, lib_sha[:12])) if traffic else pmc_note,
+                        "library_sha256": lib_sha,
+                        "algorithmic_bytes_per_launch": alg, "launch_ms": ms, "launches_per_solve": dom_launches,
+                        "forward": {"kernel": fwd_kernel, "launch_ms": fwd_ms_avg, "GBps": alg_fwd / (fwd_ms_avg * 1e-3) / 1e9,
+                                    "TFLOPs": flop_fwd / (fwd_ms_avg * 1e-3) / 1e12, "batch_evals": nfe_fwd / B},
+                        "adjoint": {"kernel": adj_kernel, "launch_ms": adj_ms_avg, "GBps": alg_adj / (adj_ms_avg * 1e-3) / 1e9,
+                                    "TFLOPs": flop_adj / (adj_ms_avg * 1e-3) / 1e12, "batch_evals": nfe_aug / B}}
         out = {
             "metric": "ODE-RHS evals/sec (genes x trajectories)", "value": value,
             "unit": "gene*trajectory RHS evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -595,22 +649,26 @@ def main(args):
                        "parallelism": "trajectory-sharded x%d, grouped gradient all-reduce" % world,
                        "nfe_forward_per_step": nfe_fwd, "nfe_augmented_per_step": nfe_aug,
                        "status_readback": args.status},
-            "roofline": roofline,
+        }
+        if args.full:
+            ws = sorted(windows)
+            out["roofline"] = roofline
             # forward and augmented evaluations are different units of work: their own rates, from the
             # launch durations of the two solve kernels on this rank
-            "rates": {"forward_evals_per_s": nfe_fwd * N / (fwd_ms_avg * 1e-3),
-                      "augmented_evals_per_s": nfe_aug * N / (adj_ms_avg * 1e-3),
-                      "kernel_ms_per_step": fwd_ms_avg + adj_ms_avg,
-                      "step_over_kernels": (elapsed / args.steps * 1e3) / (fwd_ms_avg + adj_ms_avg)},
-            "extra": {"step_windows_ms": {"windows": windows, "p50": float(np.percentile(windows, 50)),
-                                          "p90": float(np.percentile(windows, 90)), "min": ws[0], "max": ws[-1],
-                                          "note": "ms per step of six consecutive timed regions of `steps` steps each; the "
-                                                  "first is the one `value` and `ms_per_step` report"},
-                      "prewarm_steps": n_pre, "prewarm_windows_ms": [round(x, 4) for x in pre_windows]},
-        }
+            out["rates"] = {"forward_evals_per_s": nfe_fwd * N / (fwd_ms_avg * 1e-3),
+                            "augmented_evals_per_s": nfe_aug * N / (adj_ms_avg * 1e-3),
+                            "kernel_ms_per_step": fwd_ms_avg + adj_ms_avg,
+                            "step_over_kernels": (elapsed / args.steps * 1e3) / (fwd_ms_avg + adj_ms_avg)}
+        out["extra"] = {"prewarm_steps": n_pre, "prewarm_windows_ms": [round(x, 4) for x in pre_windows]}
+        if args.full:
+            out["extra"]["step_windows_ms"] = {
+                "windows": windows, "p50": float(np.percentile(windows, 50)), "p90": float(np.percentile(windows, 90)),
+                "min": ws[0], "max": ws[-1],
+                "note": "ms per step of six consecutive timed regions of `steps` steps each; the first is the one `value` "
+                        "and `ms_per_step` report"}
         if other is not None:
             out["extra"]["strong"] = other
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # informational: the reference's full training_step (train_insilico.py:124-140) with its K = 10 000-row
             # prior branch and an Adam step; NOT part of `value` (the metric counts ODE RHS evaluations only)
             try:
@@ -726,7 +784,7 @@ def main(args):
                                 "(two solve launches + layout + gradient reduction), deferred status"}
             except Exception as exc:   # noqa: BLE001
                 out["extra"]["reference_batch_error"] = repr(exc)[:200]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # both shapes BASELINE.md section 3 names; speed-ups are quoted against the stronger one
             loop = cpu_baseline(wl, net, y0, t, G)
             try:

@@ -94,7 +94,7 @@ def test_odenet_mirror_has_reference_structure():
     assert (w == 0).float().mean() >= 0.9   # nn.init.sparse_(sparsity=0.95)
 
 
-def test_checkpoint_round_trip_in_the_references_four_file_format(tmp_path):
+def test_checkpoint_round_trip_in_the_references_four_file_format(tmp_path, monkeypatch):
     """ODENet.save / load_model (odenet.py:100-133): four pickles `<name>_{prods,sums,alpha_comb,gene_multipliers}.pt`;
     a fresh network that loads them has identical parameters in the reference's parameters() order."""
     import phoenix_amd
@@ -103,7 +103,10 @@ def test_checkpoint_round_trip_in_the_references_four_file_format(tmp_path):
     with torch.no_grad():                     # the 95 %-sparse init leaves a 6-row layer all zero: give it content
         for prm in a.parameters():
             prm.add_(torch.randn_like(prm))
-    fp = str(tmp_path / "model.pt")
+    # save() inserts the suffix at the FIRST '.' of the path, as the reference does: a relative name keeps a dot in the
+    # temporary directory's path (e.g. a hidden parent directory) out of it
+    monkeypatch.chdir(tmp_path)
+    fp = "model.pt"
     a.save(fp)
     for suffix in ("_prods", "_sums", "_alpha_comb", "_gene_multipliers"):
         assert os.path.exists(str(tmp_path / ("model" + suffix + ".pt")))

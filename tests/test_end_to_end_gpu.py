@@ -13,7 +13,7 @@ from conftest import load_golden
 pytestmark = pytest.mark.gpu
 
 
-def test_simulate_train_validate_checkpoint_and_scan(tmp_path):
+def test_simulate_train_validate_checkpoint_and_scan(tmp_path, monkeypatch):
     import phoenix_amd as pa
     from phoenix_amd.analysis import gene_influence_scores
     from phoenix_amd.prior import PriorMatrix, prior_targets
@@ -52,8 +52,10 @@ def test_simulate_train_validate_checkpoint_and_scan(tmp_path):
     with torch.no_grad():
         pred = pa.odeint_adjoint(net, data[0].reshape(1, 1, N), t, method="dopri5")
     assert pred.shape == (len(t), 1, 1, N) and torch.isfinite(pred).all()
-    # checkpoint round trip: same predictions from a reloaded network
-    fp = str(tmp_path / "ckpt.pt")
+    # checkpoint round trip: same predictions from a reloaded network (save() inserts its suffixes at the FIRST '.' of
+    # the path, as the reference does: a relative name keeps a dot in the temporary directory's path out of it)
+    monkeypatch.chdir(tmp_path)
+    fp = "ckpt.pt"
     net.save(fp)
     net2 = pa.ODENet(dev, N, neurons=40)
     net2.load(fp)

@@ -9,9 +9,9 @@ for wl in breast yeast bcell insilico; do
   timeout 600 bash tools/collect_profiles.sh $wl $TAG > $OUT/collect_$wl.log 2>&1
 done
 for wl in breast yeast bcell insilico; do
-  timeout 600 python bench.py --workload $wl > profiles/${TAG}_bench_$wl.json 2> $OUT/bench_$wl.err
+  timeout 600 python bench.py --full --workload $wl > profiles/${TAG}_bench_$wl.json 2> $OUT/bench_$wl.err
 done
-timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 1 --no-cpu-baseline > profiles/${TAG}_bench_breast_torchrun_1rank.json 2> $OUT/torchrun.err
+timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus 1 --no-cpu-baseline > profiles/${TAG}_bench_breast_torchrun_1rank.json 2> $OUT/torchrun.err
 PHX_PROF=1 timeout 200 python tools/prof_segments.py breast adj > profiles/${TAG}_breast_segments_adj3.txt 2>&1
 PHX_PROF=1 timeout 200 python tools/prof_segments.py breast fwd > profiles/${TAG}_breast_segments_fwd3.txt 2>&1
 PHX_PROF=1 timeout 200 python tools/prof_segments.py breast adj 17 > profiles/${TAG}_breast_b17_segments_adj3.txt 2>&1

@@ -9,7 +9,7 @@ tail -5 $OUT/pytest.log
 for wl in $WLS; do
   for sg in ${STAGGERS:-default}; do
     if [ "$sg" != default ]; then export PHX_STAGGER_US=$sg; fi
-    timeout 600 python bench.py --workload $wl --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_${wl}_$sg.json 2> $OUT/bench_${wl}_$sg.err
+    timeout 600 python bench.py --full --workload $wl --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_${wl}_$sg.json 2> $OUT/bench_${wl}_$sg.err
     python - <<PY
 import json
 try:
