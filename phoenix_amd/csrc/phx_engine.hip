@@ -867,22 +867,6 @@ bool plan_v1(int N, int H, int B, int T, int control, int nvec, int fwidth /* hi
 }
 
 
-// Batches larger than one residency: per-trajectory control makes trajectories independent, so the host walks the
-// batch in chunks that the v1 plan accepts (pointers are offset, the [T,B,N] time stride stays B_total*N).
-int pick_chunk_v1(int N, int H, int B, int T, int control, bool adj)
-{
-    D1 d1;
-    auto ok = [&](int b) {
-        return adj ? plan_v1(N, H, b, T, control, NVEC_ADJ, 4, ADJ_LDS_EXTRA, &d1, 40, ADJ_NW_CAP)
-                   : plan_v1(N, H, b, T, control, NVEC_FWD, 2, 0, &d1);
-    };
-    if (ok(B)) return B;
-    if (control != PHX_CTRL_PER_TRAJECTORY) return 0;
-    for (int bc = 4096; bc >= 16; bc >>= 1)
-        if (bc < B && ok(bc)) return bc;
-    return 0;
-}
-
 // `calls` independent shared-control odeint calls of B/calls rows each: the largest number of calls one launch takes
 // (one batch group per call), 0 when not even a single call can be planned.
 int pick_calls_v1(int N, int H, int B, int T, int calls)
@@ -895,50 +879,255 @@ int pick_calls_v1(int N, int H, int B, int T, int calls)
     return 0;
 }
 
-struct Layout1 {
-    size_t total, cnt, part, zbuf, scratch, dtheta, prof, xbytes, wimg;
-};
+bool plan_v1_fwd(int N, int H, int B, int T, int control, int /* method: any */, D1 *out)
+{
+    return plan_v1(N, H, B, T, control, NVEC_FWD, 2, 0, out);
+}
+bool plan_v1_adj(int N, int H, int B, int T, int control, int /* method: any */, D1 *out)
+{
+    return plan_v1(N, H, B, T, control, NVEC_ADJ, 4, ADJ_LDS_EXTRA, out, 40, ADJ_NW_CAP);
+}
 
 // ftiles: hidden fragment tiles exchanged per trajectory tile (2HT forward, 4HT adjoint)
-Layout1 make_layout1(const D1 &d, int ftiles, bool grads, int zslots = 1)
+Regions make_layout1(const D1 &d, int ftiles, bool grads, int zslots)
 {
-    Layout1 L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Regions L{};
+    Take take;
     const size_t R = (size_t)d.ntg * ftiles * d.HC * 4 + d.ntg;   // hidden rows (all chunks) + norm rows per group
     L.cnt = take(4096);
     L.part = take((size_t)d.TG * d.G * R * 64 * 8);
     L.zbuf = take((size_t)zslots * d.TG * R * 64 * 8);
-    L.xbytes = off - L.part;                                // granule buffers are zeroed before every launch
+    L.xbytes = take.off - L.part;                           // granule buffers are zeroed before every launch
     L.scratch = take((size_t)d.TG * d.G * d.nvec * d.ntg * d.NB * 512 * 4);
-    const size_t PP = align_up((size_t)4 * d.H * d.N + d.N + 2 * d.H, 4);
-    L.dtheta = take(grads ? PP * 4 * d.TG * d.NW : 0);
+    L.pp = (long long)align_up((size_t)4 * d.H * d.N + d.N + 2 * d.H, 4);
+    // partials of waves that own tiles (helper waves of a single small group write none); the quadrature pass
+    // first-touches every element of them (plain stores) when T >= 2
+    L.nparts = d.TG == 1 ? (d.ntg + d.TPW - 1) / d.TPW : d.TG * d.NW;
+    L.dtheta = take(grads ? (size_t)L.pp * 4 * d.TG * d.NW : 0);
     L.prof = take((size_t)d.TG * d.G * 16 * 8);
     L.wimg = take((size_t)d.nblk * d.HC * blk_floats_ch(d.HT, d.Hc) * 4);
-    L.total = off;
+    L.total = take.off;
     return L;
 }
+Regions layout_v1_fwd(const D1 &d, bool) { return make_layout1(d, 2 * d.HT, false, 1); }
+Regions layout_v1_adj(const D1 &d, bool) { return make_layout1(d, 4 * d.HT, true, 7); }   // (partials also without gradients)
 
-W1 make_w1(void *base, const Layout1 &L)
+void pack_v1(SolveArgs &a, const phx_params *p, hipStream_t st)
 {
-    char *p = (char *)base;
-    W1 w{};
-    w.cnt = (unsigned long long *)(p + L.cnt);
-    w.abort_flag = (unsigned int *)(p + L.cnt + 2048);
-    w.part = (unsigned long long *)(p + L.part);
-    w.zbuf = (unsigned long long *)(p + L.zbuf);
-    w.scratch = (float *)(p + L.scratch);
-    w.dtheta = (float *)(p + L.dtheta);
-    const char *pe = getenv("PHX_PROF");
-    w.prof = (pe && pe[0] == '1') ? (unsigned long long *)(p + L.prof) : nullptr;
-    w.wimg = (const float *)(p + L.wimg);
-    w.hq = nullptr;
-    return w;
+    const D1 &d = a.d;
+    if (p->wimg) a.w.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
+    else
+        hipLaunchKernelGGL(k1_pack_images, dim3(d.nblk * d.HC), dim3(256), 0, st, to_net(p), (float *)a.w.wimg, d.HT, d.HC,
+                           d.Hc, blk_floats_ch(d.HT, d.Hc));
 }
 
-size_t lds_bytes_v1(const D1 &d, size_t per_block_extra)
+const void *prepare_v1_fwd(SolveArgs &a, const phx_params *p, hipStream_t st)
 {
-    return (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + per_block_extra * d.NB + ctl_bytes(d.Bt);
+    const D1 &d = a.d;
+    pack_v1(a, p, st);
+    a.lds = (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + ctl_bytes(d.Bt);
+    if (d.HC > 1)
+        return d.HT == 7 ? reinterpret_cast<const void *>(k1_solve_fwd<7, 256, true>)
+                         : reinterpret_cast<const void *>(k1_solve_fwd<8, 256, true>);
+    if (d.HT == 3)
+        return d.NW == 8 ? reinterpret_cast<const void *>(k1_solve_fwd<3, 512, false>)
+                         : reinterpret_cast<const void *>(k1_solve_fwd<3, 256, false>);
+    return reinterpret_cast<const void *>(k1_solve_fwd<8, 256, false>);
+}
+
+const void *prepare_v1_adj(SolveArgs &a, const phx_params *p, hipStream_t st)
+{
+    const D1 &d = a.d;
+    pack_v1(a, p, st);
+    a.lds = (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + ADJ_LDS_EXTRA * d.NB + ctl_bytes(d.Bt) + (size_t)40 * d.Bt;
+    if (d.HC > 1)
+        return d.HT == 7 ? reinterpret_cast<const void *>(k1_solve_adj<7, 256, true>)
+                         : reinterpret_cast<const void *>(k1_solve_adj<8, 256, true>);
+    // (HT = 3: NW <= ADJ_NW_CAP = 4, the kernel's LDS combine layout relies on it)
+    return d.HT == 3 ? reinterpret_cast<const void *>(k1_solve_adj<3, 256, false>)
+                     : reinterpret_cast<const void *>(k1_solve_adj<8, 256, false>);
+}
+
+hipError_t launch_v1_fwd(const void *fn, const SolveArgs &a, hipStream_t st)
+{
+    return launch_plain(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.y0, a.t, a.sol,
+                        a.status, a.nfe, a.nsteps);
+}
+
+hipError_t launch_v1_adj(const void *fn, const SolveArgs &a, hipStream_t st)
+{
+    return launch_plain(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.t, a.y_saved,
+                        a.grad_y, a.adj_y0, a.status, a.nfe, a.nsteps, a.grads, a.PP);
+}
+
+bool reduce_v1(const SolveArgs &a, int npart, const phx_grads *g, int overwrite, hipStream_t st)
+{
+    return launch_reduce_grads(a.w.dtheta, npart, a.PP, a.d.N, a.d.H, g, overwrite, st);
+}
+
+const Backend &v1_fwd_backend()
+{
+    static const Backend b = {1, false, false, false,
+                                    plan_v1_fwd, layout_v1_fwd, plan6_ht, prepare_v1_fwd, launch_v1_fwd, nullptr};
+    return b;
+}
+const Backend &v1_adj_backend()
+{
+    static const Backend b = {1, false, false, false,
+                                    plan_v1_adj, layout_v1_adj, plan6_ht, prepare_v1_adj, launch_v1_adj, reduce_v1};
+    return b;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the persistent solve kernels of each direction, in the order they are tried, and the chunk driver
+// ---------------------------------------------------------------------------------------------------
+const Backend *const *backends(int op)
+{
+    static const Backend *const fwd[] = {&fwd3_backend(), &fwd3c_backend(), &v1_fwd_backend(), nullptr};
+    static const Backend *const adj[] = {&adj3_backend(), &adj3c_backend(), &adj2_backend(), &v1_adj_backend(), nullptr};
+    static const Backend *const none[] = {nullptr};
+    return op == PHX_OP_ODEINT ? fwd : op == PHX_OP_ADJOINT ? adj : none;
+}
+
+// Trajectories per launch: B when one launch takes the batch; else, under per-trajectory control (trajectories are
+// independent), the largest power of two <= 4096 that the plan accepts; 0: no plan.
+int pick_chunk(const Backend &be, int N, int H, int B, int T, int control, int method)
+{
+    D1 d;
+    if (be.plan(N, H, B, T, control, method, &d)) return B;
+    if (control != PHX_CTRL_PER_TRAJECTORY) return 0;
+    for (int bc = 4096; bc >= 16; bc >>= 1)
+        if (bc < B && be.plan(N, H, bc, T, control, method, &d)) return bc;
+    return 0;
+}
+
+struct Pick {
+    const Backend *be;   // null: no persistent kernel plans the batch (the VALU engine takes it in one launch)
+    int chunk;
+};
+
+// the first kernel of the direction that plans the batch; whole: only a plan of the whole batch in one launch counts
+Pick first_backend(int op, int N, int H, int B, int T, int control, int method, bool whole = false)
+{
+    for (const Backend *const *b = backends(op); *b; ++b) {
+        D1 d;
+        const int chunk = !whole ? pick_chunk(**b, N, H, B, T, control, method)
+                                 : (*b)->plan(N, H, B, T, control, method, &d) ? B : 0;
+        if (chunk > 0) return {*b, chunk};
+    }
+    return {nullptr, 0};
+}
+
+SolveCfg solve_cfg(const phx_solve_opts *o)
+{
+    SolveCfg cfg;
+    cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
+    cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
+    cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
+    return cfg;
+}
+
+// one phx_odeint / phx_odeint_adjoint_backward call: the caller's arrays of the whole batch (forward: y0, sol; backward:
+// y_saved, grad_y, adj_y0, grads)
+struct SolveCall {
+    const phx_params *p;
+    const phx_solve_opts *o;
+    int B, T;
+    const double *t;
+    const float *y0, *y_saved, *grad_y;
+    float *sol, *adj_y0;
+    int *status, *nfe, *nsteps;
+    const phx_grads *grads;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t st;
+};
+
+// diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
+// the call fails between its launches
+struct EventPair {
+    hipStream_t st;
+    bool open = false;
+    void begin() { ev_begin(st); open = true; }
+    void end()
+    {
+        if (open) ev_end(st);
+        open = false;
+    }
+    ~EventPair() { end(); }
+};
+
+// Runs a batch on kernel family `be` in launches of `chunk` trajectories: pointers are offset to a launch's rows, the
+// [T,B,N] time stride stays B*N, later launches add their parameter gradients.  plan(bc, &d): the plan of a launch of bc.
+template <typename Plan>
+int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
+{
+    const phx_params *p = c.p;
+    const phx_solve_opts *o = c.o;
+    SolveArgs a{};
+    a.net = to_net(p);
+    a.cfg = solve_cfg(o);
+    a.grads = c.grads ? 1 : 0;
+    const char *pe = getenv("PHX_PROF");   // segment timers (Backend::prof_levels); 2, 3: finer timers of some kernels
+    const int plevel = pe ? atoi(pe) : 0;
+    const bool prof = be.prof_levels ? plevel >= 1 : (pe && pe[0] == '1');
+    EventPair ev{c.st};
+    for (int b0 = 0; b0 < c.B; b0 += chunk) {
+        D1 &d = a.d;
+        if (!plan(std::min(chunk, c.B - b0), &d)) return PHX_ERR_BAD_ARG;
+        d.BN = (long long)c.B * p->N;   // time stride of the caller's [T,B,N] arrays
+        const long long r0 = (long long)b0 * p->N;
+        auto rows = [&](auto *q) { return q ? q + r0 : q; };
+        a.t = !o->t_per_sample ? c.t   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
+              : reinterpret_cast<const double *>(reinterpret_cast<const char *>(c.t) +
+                                                 (size_t)b0 * c.T * (o->t_is_f32 == 2 ? 4 : 8));
+        a.y0 = rows(c.y0); a.sol = rows(c.sol);
+        a.y_saved = rows(c.y_saved); a.grad_y = rows(c.grad_y); a.adj_y0 = rows(c.adj_y0);
+        a.status = c.status + b0; a.nfe = c.nfe + b0; a.nsteps = c.nsteps + b0;
+        const Regions L = be.layout(d, c.grads != nullptr);
+        if (c.workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
+        char *base = (char *)c.workspace;
+        W1 &w = a.w;
+        w.cnt = (unsigned long long *)(base + L.cnt);
+        w.abort_flag = (unsigned int *)(base + L.cnt + 2048);
+        w.part = (unsigned long long *)(base + L.part);
+        w.zbuf = (unsigned long long *)(base + L.zbuf);
+        w.part1 = (unsigned long long *)(base + L.part1);
+        w.zbuf1 = (unsigned long long *)(base + L.zbuf1);
+        w.scratch = (float *)(base + L.scratch);
+        w.dtheta = (float *)(base + L.dtheta);
+        w.prof = prof ? (unsigned long long *)(base + L.prof) : nullptr;
+        w.prof_level = plevel;
+        w.wimg = (const float *)(base + L.wimg);
+        w.hq = (float *)(base + L.hq);
+        a.PP = L.pp;
+        // header + exchange buffers are contiguous: one fill -- unless the caller vouches for the workspace (ws_keep: the
+        // previous call on it was this one, same shape, same options), the batch is one launch and the kernel cleans
+        // its idle exchange set itself (the kernels then alternate between the two sets)
+        const bool fill = !(be.cleans_idle_set && o->ws_keep && chunk >= c.B);
+        if (fill && hipMemsetAsync(w.cnt, 0, L.part - L.cnt + L.xbytes, c.st) != hipSuccess) return PHX_ERR_LAUNCH;
+        if (c.grads && (be.zero_dtheta_always || c.T < 2) &&
+            hipMemsetAsync(w.dtheta, 0, sizeof(float) * (size_t)L.pp * L.nparts, c.st) != hipSuccess)
+            return PHX_ERR_LAUNCH;
+        const void *fn = be.prepare(a, p, c.st);
+        if (!fn) return PHX_ERR_BAD_ARG;
+        // the workgroups of a launch wait for each other's rows: refuse a grid the device cannot hold at once
+        if (!set_lds_fn(fn, a.lds) || !fits_resident(fn, 64 * d.NW, a.lds, d.TG * d.G)) return PHX_ERR_LAUNCH;
+        if (b0 == 0) ev.begin();
+        const hipError_t lerr = be.launch(fn, a, c.st);
+        if (b0 + chunk >= c.B) ev.end();
+        if (lerr != hipSuccess || hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
+        if (c.grads && !be.reduce(a, L.nparts, c.grads, (c.grads->overwrite && b0 == 0) ? 1 : 0, c.st))   // later ones add
+            return PHX_ERR_LAUNCH;
+    }
+    return PHX_OK;
+}
+
+int run_solve(const Pick &k, const SolveCall &c)
+{
+    const Backend &be = *k.be;
+    return run_solve(be, k.chunk, [&](int bc, D1 *d) { return be.plan(c.p->N, c.p->H, bc, c.T, c.o->control, c.o->method, d); },
+                     c);
 }
 
 
@@ -1380,21 +1569,12 @@ void phx_debug_set_kernel_events(void *ev_start, void *ev_stop)
 int phx_debug_profile_region(int op, int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups,
                              int *plan /* [NW, TPW, NB, G, TG, HT] */)
 {
+    const Pick k = first_backend(op, N, H, B, T, control, PHX_DOPRI5, true);   // (the plan of a one-launch batch)
     D1 d1;
-    if (op != PHX_OP_ODEINT && op != PHX_OP_ADJOINT) return PHX_ERR_BAD_ARG;
-    const bool adj = op == PHX_OP_ADJOINT;
-    if (!adj && fwd3_profile_region(N, H, B, T, control, offset, n_workgroups, plan) == PHX_OK) return PHX_OK;
-    if (!adj && fwd3c_profile_region(N, H, B, T, control, offset, n_workgroups, plan) == PHX_OK) return PHX_OK;
-    if (adj && adj3_profile_region(N, H, B, T, control, offset, n_workgroups, plan) == PHX_OK) return PHX_OK;
-    if (adj && adj3c_profile_region(N, H, B, T, control, offset, n_workgroups, plan) == PHX_OK) return PHX_OK;
-    if (adj && adj2_profile_region(N, H, B, T, control, offset, n_workgroups, plan) == PHX_OK) return PHX_OK;
-    if (!plan_v1(N, H, B, T, control, adj ? NVEC_ADJ : NVEC_FWD, 2, adj ? ADJ_LDS_EXTRA : 0, &d1, adj ? 40 : 0,
-                 adj ? ADJ_NW_CAP : 8))
-        return PHX_ERR_BAD_ARG;
-    const Layout1 L1 = make_layout1(d1, adj ? 4 * d1.HT : 2 * d1.HT, adj, adj ? 7 : 1);
-    *offset = L1.prof;
+    if (!k.be || !k.be->plan(N, H, B, T, control, PHX_DOPRI5, &d1)) return PHX_ERR_BAD_ARG;
+    *offset = k.be->layout(d1, true).prof;
     *n_workgroups = d1.TG * d1.G;
-    if (plan) { plan[0] = d1.NW; plan[1] = d1.TPW; plan[2] = d1.NB; plan[3] = d1.G; plan[4] = d1.TG; plan[5] = d1.HT; }
+    if (plan) { plan[0] = d1.NW; plan[1] = d1.TPW; plan[2] = d1.NB; plan[3] = d1.G; plan[4] = d1.TG; plan[5] = k.be->plan6(d1); }
     return PHX_OK;
 }
 
@@ -1405,33 +1585,22 @@ int phx_debug_adjoint_kernel(int N, int H, int B, int T, int control)
 
 int phx_debug_adjoint_kernel_m(int N, int H, int B, int T, int control, int method)
 {
-    if (adj3_chunk(N, H, B, T, control, method) > 0) return 3;
-    if (adj3c_chunk(N, H, B, T, control, method) > 0) return 4;   // third generation, chunked hidden layer (H > 48)
-    if (adj2_chunk(N, H, B, T, control) > 0) return 2;
-    return pick_chunk_v1(N, H, B, T, control, true) > 0 ? 1 : 0;
+    const Pick k = first_backend(PHX_OP_ADJOINT, N, H, B, T, control, method);
+    return k.be ? k.be->id : 0;
 }
 
 int phx_debug_forward_kernel_m(int N, int H, int B, int T, int control, int method)
 {
-    if (fwd3_chunk(N, H, B, T, control, method) > 0) return 3;
-    if (fwd3c_chunk(N, H, B, T, control, method) > 0) return 4;   // third generation, chunked hidden layer (H > 48)
-    return pick_chunk_v1(N, H, B, T, control, false) > 0 ? 1 : 0;
+    const Pick k = first_backend(PHX_OP_ODEINT, N, H, B, T, control, method);
+    return k.be ? k.be->id : 0;
 }
 
 int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, int method)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 0 || (op != PHX_OP_ODEINT && op != PHX_OP_ADJOINT)) return 0;
-    int chunk = 0;
-    if (op == PHX_OP_ADJOINT) {
-        if ((chunk = adj3_chunk(N, H, B, T, control, method)) <= 0 && (chunk = adj3c_chunk(N, H, B, T, control, method)) <= 0 &&
-            (chunk = adj2_chunk(N, H, B, T, control)) <= 0)
-            chunk = pick_chunk_v1(N, H, B, T, control, true);
-    } else {
-        if ((chunk = fwd3_chunk(N, H, B, T, control, method)) <= 0 && (chunk = fwd3c_chunk(N, H, B, T, control, method)) <= 0)
-            chunk = pick_chunk_v1(N, H, B, T, control, false);
-    }
-    if (chunk <= 0) return 1;   // the VALU engine takes any batch in one launch
-    return (B + chunk - 1) / chunk;
+    const Pick k = first_backend(op, N, H, B, T, control, method);
+    if (!k.be) return 1;   // the VALU engine takes any batch in one launch
+    return (B + k.chunk - 1) / k.chunk;
 }
 
 size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
@@ -1439,16 +1608,16 @@ size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
     if (N <= 0 || H <= 0 || B <= 0 || T < 0) return 0;
     const Dims d = make_dims(N, H, B, T, PHX_CTRL_PER_TRAJECTORY);
     size_t need = make_layout(d, op).total;
-    if (op == PHX_OP_ODEINT) {
-        need = std::max(need, fwd3_workspace_bytes(N, H, B, T));
-        need = std::max(need, fwd3c_workspace_bytes(N, H, B, T));
-        D1 d1;
+    // every persistent kernel of a solve direction under both control modes: the launches of the chunk size and the
+    // remainder launch (a smaller batch can plan more groups or twice the gene tiles: a larger layout)
+    for (const Backend *const *b = backends(op); *b; ++b)
         for (int ctl = 0; ctl < 2; ++ctl) {
-            const int bc = pick_chunk_v1(N, H, B, T, ctl, false);
-            if (bc > 0 && plan_v1(N, H, bc, T, ctl, NVEC_FWD, 2, 0, &d1))
-                need = std::max(need, make_layout1(d1, 2 * d1.HT, false).total);
+            const int chunk = pick_chunk(**b, N, H, B, T, ctl, PHX_DOPRI5);
+            for (const int bc : {chunk, chunk > 0 ? B % chunk : 0}) {
+                D1 d1;
+                if (bc > 0 && (*b)->plan(N, H, bc, T, ctl, PHX_DOPRI5, &d1)) need = std::max(need, (*b)->layout(d1, true).total);
+            }
         }
-    }
     if (op == PHX_OP_RHS_FORWARD) {
         PlanBatch pb;
         if (plan_batch(N, H, B, &pb)) need = std::max(need, pb.total_fwd);   // (whether the chain runs depends on the call's images)
@@ -1461,17 +1630,6 @@ size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
         PlanEval pe;
         for (int nbc = (H <= 48 ? 2 : EVAL_NBC_HT8); nbc <= (H <= 48 ? EVAL_NBC_HT3_MAX : EVAL_NBC_HT8); ++nbc)
             if (plan_eval(N, H, B, nbc, &pe)) need = std::max(need, make_layout_eval(pe, true).total);
-    }
-    if (op == PHX_OP_ADJOINT) {
-        need = std::max(need, adj2_workspace_bytes(N, H, B, T));
-        need = std::max(need, adj3_workspace_bytes(N, H, B, T));
-        need = std::max(need, adj3c_workspace_bytes(N, H, B, T));
-        D1 d1;
-        for (int ctl = 0; ctl < 2; ++ctl) {
-            const int bc = pick_chunk_v1(N, H, B, T, ctl, true);
-            if (bc > 0 && plan_v1(N, H, bc, T, ctl, NVEC_ADJ, 4, ADJ_LDS_EXTRA, &d1, 40, ADJ_NW_CAP))
-                need = std::max(need, make_layout1(d1, 4 * d1.HT, true, 7).total);
-        }
     }
     return need;
 }
@@ -1510,7 +1668,7 @@ size_t phx_odeint_calls_workspace_bytes(int N, int H, int B, int T, int calls)
     const int n = pick_calls_v1(N, H, B, T, calls);
     D1 d1;
     if (n < 1 || !plan_v1(N, H, n * (B / calls), T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, &d1, 0, 8, n)) return 0;
-    return make_layout1(d1, 2 * d1.HT, false).total;
+    return layout_v1_fwd(d1, false).total;
 }
 
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,
@@ -1653,81 +1811,20 @@ int phx_odeint(const phx_params *p, const float *y0_all, const double *t_all, in
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    SolveCfg cfg;
-    cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
-    cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
-    cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
+    const SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
+                      workspace, workspace_bytes, st};
     // several calls in one batch (analysis callers): every call keeps its own shared controller, a launch takes as many
-    // calls as there are batch groups to run them (MFMA kernels only)
-    const int calls = o->calls > 1 ? o->calls : 1;
-    int Bcall = 0;
-    if (calls > 1) {
-        if (o->control != PHX_CTRL_SHARED || B % calls != 0) return PHX_ERR_BAD_ARG;
-        Bcall = B / calls;
+    // calls as there are batch groups to run them (first-generation kernel only)
+    if (o->calls > 1) {
+        if (o->control != PHX_CTRL_SHARED || B % o->calls != 0) return PHX_ERR_BAD_ARG;
+        const int Bcall = B / o->calls, chunk = pick_calls_v1(p->N, p->H, B, T, o->calls) * Bcall;
+        if (chunk == 0) return PHX_ERR_BAD_ARG;
+        return run_solve(v1_fwd_backend(), chunk, [&](int bc, D1 *d) {
+            return plan_v1(p->N, p->H, bc, T, o->control, NVEC_FWD, 2, 0, d, 0, 8, bc / Bcall);
+        }, c);
     }
-    // third-generation forward kernel (dopri5, narrow hidden layer; phx_fwd3.hip)
-    if (!Bcall && fwd3_chunk(p->N, p->H, B, T, o->control, o->method) > 0)
-        return fwd3_run(p, y0_all, t_all, B, T, o, sol_all, status_all, nfe_all, nsteps_all, workspace, workspace_bytes, st);
-    // ... and its hidden-chunked form for wide hidden layers (H > 48: the yeast and B-cell shapes; phx_fwd3c.hip)
-    if (!Bcall && fwd3c_chunk(p->N, p->H, B, T, o->control, o->method) > 0)
-        return fwd3c_run(p, y0_all, t_all, B, T, o, sol_all, status_all, nfe_all, nsteps_all, workspace, workspace_bytes, st);
-    // v1: MFMA kernels with LDS-resident weights, when the shape fits (large batches: in chunks)
-    const int chunk_f = Bcall ? pick_calls_v1(p->N, p->H, B, T, calls) * Bcall : pick_chunk_v1(p->N, p->H, B, T, o->control, false);
-    if (Bcall && chunk_f == 0) return PHX_ERR_BAD_ARG;
-    for (int b0 = 0; chunk_f > 0 && b0 < B; b0 += chunk_f) {
-        D1 d1;
-        const int bc = std::min(chunk_f, B - b0);
-        if (!plan_v1(p->N, p->H, bc, T, o->control, NVEC_FWD, 2, 0, &d1, 0, 8, Bcall ? bc / Bcall : 1)) return PHX_ERR_BAD_ARG;
-        d1.BN = (long long)B * p->N;   // time stride of the caller's [T,B,N] arrays
-        {
-            const float *y0 = y0_all + (long long)b0 * p->N;
-            const double *t = !o->t_per_sample ? t_all   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
-                              : reinterpret_cast<const double *>(reinterpret_cast<const char *>(t_all) +
-                                                                 (size_t)b0 * T * (o->t_is_f32 == 2 ? 4 : 8));
-            float *sol = sol_all + (long long)b0 * p->N;
-            int *status = status_all + b0, *nfe = nfe_all + b0, *nsteps = nsteps_all + b0;
-            const Layout1 L1 = make_layout1(d1, 2 * d1.HT, false);
-            if (workspace_bytes < L1.total) return PHX_ERR_WORKSPACE;
-            W1 w1 = make_w1(workspace, L1);
-            const size_t lds = lds_bytes_v1(d1, 0);
-            // counters + granule buffers are contiguous: one fill
-            if (hipMemsetAsync(w1.cnt, 0, L1.part - L1.cnt + L1.xbytes, st) != hipSuccess) return PHX_ERR_LAUNCH;
-            const dim3 grid1(d1.TG * d1.G), blk1(64 * d1.NW);
-            if (p->wimg) w1.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
-            else
-                hipLaunchKernelGGL(k1_pack_images, dim3(d1.nblk * d1.HC), dim3(256), 0, st, to_net(p), (float *)w1.wimg, d1.HT,
-                                   d1.HC, d1.Hc, blk_floats_ch(d1.HT, d1.Hc));
-            ev_begin(st);
-            if (d1.HC > 1 && d1.HT == 7) {
-                if (!set_lds_resident(k1_solve_fwd<7, 256, true>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_fwd<7, 256, true>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t,
-                                   sol, status, nfe, nsteps);
-            } else if (d1.HC > 1) {
-                if (!set_lds_resident(k1_solve_fwd<8, 256, true>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_fwd<8, 256, true>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t,
-                                   sol, status, nfe, nsteps);
-            } else if (d1.HT == 3 && d1.NW == 8) {
-                if (!set_lds_resident(k1_solve_fwd<3, 512, false>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_fwd<3, 512, false>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t,
-                                   sol, status, nfe, nsteps);
-            } else if (d1.HT == 3) {
-                if (!set_lds_resident(k1_solve_fwd<3, 256, false>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_fwd<3, 256, false>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t,
-                                   sol, status, nfe, nsteps);
-            } else {
-                if (!set_lds_resident(k1_solve_fwd<8, 256, false>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_fwd<8, 256, false>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t,
-                                   sol, status, nfe, nsteps);
-            }
-            ev_end(st);
-            if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
-        }
-    }
-    if (chunk_f > 0) return PHX_OK;
-    const float *y0 = y0_all;
-    const double *t = t_all;
-    float *sol = sol_all;
-    int *status = status_all, *nfe = nfe_all, *nsteps = nsteps_all;
+    const Pick k = first_backend(PHX_OP_ODEINT, p->N, p->H, B, T, o->control, o->method);
+    if (k.be) return run_solve(k, c);
     const Dims d = make_dims(p->N, p->H, B, T, o->control);
     const Layout L = make_layout(d, PHX_OP_ODEINT);
     if (workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
@@ -1737,8 +1834,8 @@ int phx_odeint(const phx_params *p, const float *y0_all, const double *t_all, in
     if (!fits_resident(reinterpret_cast<const void *>(k_solve_fwd), NT, 0, grid)) return PHX_ERR_LAUNCH;   // grid barriers inside
     if (hipMemsetAsync(w.sync, 0, sizeof(SyncBlock), st) != hipSuccess) return PHX_ERR_LAUNCH;
     ev_begin(st);
-    hipLaunchKernelGGL(k_solve_fwd, dim3(grid), dim3(NT), 0, st, to_net(p), d, w, cfg, y0, t, sol, status, nfe,
-                       nsteps);
+    hipLaunchKernelGGL(k_solve_fwd, dim3(grid), dim3(NT), 0, st, to_net(p), d, w, solve_cfg(o), y0_all, t_all, sol_all,
+                       status_all, nfe_all, nsteps_all);
     ev_end(st);
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
 }
@@ -1756,85 +1853,10 @@ int phx_odeint_adjoint_backward(const phx_params *p, const double *t_all, int B,
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    SolveCfg cfg;
-    cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
-    cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
-    cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
-    // third kernel (dopri5, narrow hidden layer exchanged among many gene tiles: the breast-cancer shape; phx_adj3.hip)
-    if (adj3_chunk(p->N, p->H, B, T, o->control, o->method) > 0)
-        return adj3_run(p, t_all, B, T, o, y_saved_all, grad_y_all, adj_y0_all, grads, status_all, nfe_all, nsteps_all,
-                        workspace, workspace_bytes, st);
-    // ... and its hidden-chunked form for wide hidden layers (H > 48: the yeast and B-cell shapes; phx_adj3c.hip)
-    if (adj3c_chunk(p->N, p->H, B, T, o->control, o->method) > 0)
-        return adj3c_run(p, t_all, B, T, o, y_saved_all, grad_y_all, adj_y0_all, grads, status_all, nfe_all, nsteps_all,
-                         workspace, workspace_bytes, st);
-    // second-generation MFMA kernel (wave pairs, fused sweeps): hidden layers that stay LDS resident (phx_adj2.hip)
-    if (adj2_chunk(p->N, p->H, B, T, o->control) > 0)
-        return adj2_run(p, t_all, B, T, o, y_saved_all, grad_y_all, adj_y0_all, grads, status_all, nfe_all, nsteps_all,
-                        workspace, workspace_bytes, st);
-    // v1: MFMA kernels (large batches: in chunks; every chunk's partials are added into `grads`)
-    const int chunk_a = pick_chunk_v1(p->N, p->H, B, T, o->control, true);
-    for (int b0 = 0; chunk_a > 0 && b0 < B; b0 += chunk_a) {
-        D1 d1;
-        const int bc = std::min(chunk_a, B - b0);
-        if (!plan_v1(p->N, p->H, bc, T, o->control, NVEC_ADJ, 4, ADJ_LDS_EXTRA, &d1, 40, ADJ_NW_CAP)) return PHX_ERR_BAD_ARG;
-        d1.BN = (long long)B * p->N;
-        {
-            const double *t = !o->t_per_sample ? t_all   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
-                              : reinterpret_cast<const double *>(reinterpret_cast<const char *>(t_all) +
-                                                                 (size_t)b0 * T * (o->t_is_f32 == 2 ? 4 : 8));
-            const float *y_saved = y_saved_all + (long long)b0 * p->N, *grad_y = grad_y_all + (long long)b0 * p->N;
-            float *adj_y0 = adj_y0_all + (long long)b0 * p->N;
-            int *status = status_all + b0, *nfe = nfe_all + b0, *nsteps = nsteps_all + b0;
-            const Layout1 L1 = make_layout1(d1, 4 * d1.HT, true, 7);
-            if (workspace_bytes < L1.total) return PHX_ERR_WORKSPACE;
-            W1 w1 = make_w1(workspace, L1);
-            const size_t lds = lds_bytes_v1(d1, ADJ_LDS_EXTRA) + (size_t)40 * d1.Bt;
-            const long long PP = (long long)align_up((size_t)4 * p->H * p->N + p->N + 2 * p->H, 4);
-            // counters + granule buffers are contiguous: one fill
-            if (hipMemsetAsync(w1.cnt, 0, L1.part - L1.cnt + L1.xbytes, st) != hipSuccess) return PHX_ERR_LAUNCH;
-            // the quadrature pass first-touches every element of every partial (plain stores) when T >= 2
-            if (grads && T < 2 && hipMemsetAsync(w1.dtheta, 0, sizeof(float) * (size_t)PP * d1.TG * d1.NW, st) != hipSuccess)
-                return PHX_ERR_LAUNCH;
-            const dim3 grid1(d1.TG * d1.G), blk1(64 * d1.NW);
-            if (p->wimg) w1.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
-            else
-                hipLaunchKernelGGL(k1_pack_images, dim3(d1.nblk * d1.HC), dim3(256), 0, st, to_net(p), (float *)w1.wimg, d1.HT,
-                                   d1.HC, d1.Hc, blk_floats_ch(d1.HT, d1.Hc));
-            ev_begin(st);
-            if (d1.HC > 1 && d1.HT == 7) {
-                if (!set_lds_resident(k1_solve_adj<7, 256, true>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_adj<7, 256, true>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, t,
-                                   y_saved, grad_y, adj_y0, status, nfe, nsteps, grads ? 1 : 0, PP);
-            } else if (d1.HC > 1) {
-                if (!set_lds_resident(k1_solve_adj<8, 256, true>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_adj<8, 256, true>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, t,
-                                   y_saved, grad_y, adj_y0, status, nfe, nsteps, grads ? 1 : 0, PP);
-            } else if (d1.HT == 3) {   // NW <= ADJ_NW_CAP = 4 (the kernel's LDS combine layout relies on it)
-                if (!set_lds_resident(k1_solve_adj<3, 256, false>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_adj<3, 256, false>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, t,
-                                   y_saved, grad_y, adj_y0, status, nfe, nsteps, grads ? 1 : 0, PP);
-            } else {
-                if (!set_lds_resident(k1_solve_adj<8, 256, false>, lds, (int)blk1.x, (int)grid1.x)) return PHX_ERR_LAUNCH;
-                hipLaunchKernelGGL((k1_solve_adj<8, 256, false>), grid1, blk1, lds, st, to_net(p), d1, w1, cfg, t,
-                                   y_saved, grad_y, adj_y0, status, nfe, nsteps, grads ? 1 : 0, PP);
-            }
-            ev_end(st);
-            if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
-            if (grads) {
-                // partials of waves that own tiles (helper waves of a single small group write none); later chunks of a
-                // large batch add
-                if (!launch_reduce_grads(w1.dtheta, d1.TG == 1 ? (d1.ntg + d1.TPW - 1) / d1.TPW : d1.TG * d1.NW, PP, p->N,
-                                         p->H, grads, (grads->overwrite && b0 == 0) ? 1 : 0, st))
-                    return PHX_ERR_LAUNCH;
-            }
-        }
-    }
-    if (chunk_a > 0) return PHX_OK;
-    const double *t = t_all;
-    const float *y_saved = y_saved_all, *grad_y = grad_y_all;
-    float *adj_y0 = adj_y0_all;
-    int *status = status_all, *nfe = nfe_all, *nsteps = nsteps_all;
+    const Pick k = first_backend(PHX_OP_ADJOINT, p->N, p->H, B, T, o->control, o->method);
+    if (k.be)
+        return run_solve(k, SolveCall{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all,
+                                      nfe_all, nsteps_all, grads, workspace, workspace_bytes, st});
     const Dims d = make_dims(p->N, p->H, B, T, o->control);
     const Layout L = make_layout(d, PHX_OP_ADJOINT);
     if (workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
@@ -1845,8 +1867,8 @@ int phx_odeint_adjoint_backward(const phx_params *p, const double *t_all, int B,
     if (hipMemsetAsync(w.sync, 0, sizeof(SyncBlock), st) != hipSuccess) return PHX_ERR_LAUNCH;
     if (hipMemsetAsync(w.dtheta, 0, sizeof(float) * (size_t)d.PP * d.GB, st) != hipSuccess) return PHX_ERR_LAUNCH;
     ev_begin(st);
-    hipLaunchKernelGGL(k_solve_adj, dim3(grid), dim3(NT), 0, st, to_net(p), d, w, cfg, t, y_saved, grad_y, adj_y0,
-                       status, nfe, nsteps, grads ? 1 : 0);
+    hipLaunchKernelGGL(k_solve_adj, dim3(grid), dim3(NT), 0, st, to_net(p), d, w, solve_cfg(o), t_all, y_saved_all, grad_y_all,
+                       adj_y0_all, status_all, nfe_all, nsteps_all, grads ? 1 : 0);
     ev_end(st);
     if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
     if (grads) return launch_reduce(d, w, grads, st);

@@ -73,36 +73,21 @@ bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
     return true;
 }
 
-int pick_chunk_fwd3(int N, int H, int B, int T, int control, int method)
+Regions make_layout_f3(const D1 &d, bool)
 {
-    D1 d1;
-    if (plan_fwd3(N, H, B, T, control, method, &d1)) return B;
-    if (control != PHX_CTRL_PER_TRAJECTORY) return 0;
-    for (int bc = 4096; bc >= 16; bc >>= 1)
-        if (bc < B && plan_fwd3(N, H, bc, T, control, method, &d1)) return bc;
-    return 0;
-}
-
-struct LayoutF3 {
-    size_t total, cnt, part, zbuf, part1, zbuf1, scratch, prof, xbytes, wimg;
-};
-
-LayoutF3 make_layout_f3(const D1 &d)
-{
-    LayoutF3 L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Regions L{};
+    Take take;
     const size_t R = (size_t)d.ntg * 2 * d.HT * 4 + d.ntg;   // hidden rows + norm rows per group
     L.cnt = take(4096);
     L.part = take((size_t)d.TG * d.G * R * 64 * 8);
     L.zbuf = take((size_t)d.TG * R * 64 * 8);
-    L.xbytes = off - L.part;                                 // header + set 0: what a fill covers (phx_mfma_v3common.inc: XSet)
+    L.xbytes = take.off - L.part;                            // header + set 0: what a fill covers (phx_mfma_v3common.inc: XSet)
     L.part1 = take((size_t)d.TG * d.G * R * 64 * 8);         // set 1: cleaned by the launch that works in set 0
     L.zbuf1 = take((size_t)d.TG * R * 64 * 8);
     L.scratch = take((size_t)d.TG * d.G * NVEC_FWD3 * d.ntg * d.NB * 512 * 4);
     L.prof = take((size_t)d.TG * d.G * 16 * 8);
     L.wimg = take((size_t)d.nblk * blk_floats_ch(d.HT, d.H) * 4);
-    L.total = off;
+    L.total = take.off;
     return L;
 }
 
@@ -112,99 +97,36 @@ size_t lds_bytes_fwd3(const D1 &d)
            (v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1 ? v3_comb_bytes(d.NW, 2 * d.HT) : 0);
 }
 
+const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
+{
+    const D1 &d = a.d;
+    if (p->wimg) a.w.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
+    else
+        hipLaunchKernelGGL(k1_pack_images, dim3(d.nblk), dim3(256), 0, st, to_net(p), (float *)a.w.wimg, d.HT, 1, p->H,
+                           blk_floats_ch(d.HT, p->H));
+    a.lds = lds_bytes_fwd3(d);
+    // HALF: the last hidden tile has at most 8 live rows (H <= 40 with three tiles; rho16 in phx_mfma_v3common.inc)
+    const char *eh = getenv("PHX_V3_HALF");   // diagnostic: 0 = full last tile also where half of it is padding
+    const bool half = p->H <= 16 * (d.HT - 1) + 8 && !(eh && eh[0] == '0');
+    const bool split = v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1;   // small batch: the waves of a tile split its blocks
+    return split ? (half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, true>)
+                         : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, true>))
+                 : (half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false>)
+                         : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, false>));
+}
+
+hipError_t launch_fwd3(const void *fn, const SolveArgs &a, hipStream_t st)
+{
+    return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.y0, a.t, a.sol,
+                             a.status, a.nfe, a.nsteps);
+}
+
 }  // namespace
 
 namespace phxh {
-
-int fwd3_chunk(int N, int H, int B, int T, int control, int method) { return pick_chunk_fwd3(N, H, B, T, control, method); }
-
-size_t fwd3_workspace_bytes(int N, int H, int B, int T)
+const Backend &fwd3_backend()
 {
-    size_t need = 0;
-    for (int ctl = 0; ctl < 2; ++ctl) {
-        D1 d1;
-        const int bc = pick_chunk_fwd3(N, H, B, T, ctl, PHX_DOPRI5);
-        if (bc > 0 && plan_fwd3(N, H, bc, T, ctl, PHX_DOPRI5, &d1)) need = std::max(need, make_layout_f3(d1).total);
-    }
-    return need;
+    static const Backend b = {3, true, false, true, plan_fwd3, make_layout_f3, plan6_ht, prepare_fwd3, launch_fwd3, nullptr};
+    return b;
 }
-
-int fwd3_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6)
-{
-    D1 d1;
-    if (!plan_fwd3(N, H, B, T, control, PHX_DOPRI5, &d1)) return PHX_ERR_BAD_ARG;
-    *offset = make_layout_f3(d1).prof;
-    *n_workgroups = d1.TG * d1.G;
-    if (plan6) { plan6[0] = d1.NW; plan6[1] = d1.TPW; plan6[2] = d1.NB; plan6[3] = d1.G; plan6[4] = d1.TG; plan6[5] = d1.HT; }
-    return PHX_OK;
-}
-
-int fwd3_run(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
-             float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes,
-             hipStream_t st)
-{
-    SolveCfg cfg;
-    cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
-    cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
-    cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
-    const int chunk = pick_chunk_fwd3(p->N, p->H, B, T, o->control, o->method);
-    if (chunk <= 0) return PHX_ERR_BAD_ARG;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        D1 d1;
-        const int bc = std::min(chunk, B - b0);
-        if (!plan_fwd3(p->N, p->H, bc, T, o->control, o->method, &d1)) return PHX_ERR_BAD_ARG;
-        d1.BN = (long long)B * p->N;   // time stride of the caller's [T,B,N] arrays
-        const float *y0 = y0_all + (long long)b0 * p->N;
-        const double *t = !o->t_per_sample ? t_all   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
-                          : reinterpret_cast<const double *>(reinterpret_cast<const char *>(t_all) +
-                                                             (size_t)b0 * T * (o->t_is_f32 == 2 ? 4 : 8));
-        float *sol = sol_all + (long long)b0 * p->N;
-        int *status = status_all + b0, *nfe = nfe_all + b0, *nsteps = nsteps_all + b0;
-        const LayoutF3 L = make_layout_f3(d1);
-        if (workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
-        char *base = (char *)workspace;
-        W1 w1{};
-        w1.cnt = (unsigned long long *)(base + L.cnt);
-        w1.abort_flag = (unsigned int *)(base + L.cnt + 2048);
-        w1.part = (unsigned long long *)(base + L.part);
-        w1.zbuf = (unsigned long long *)(base + L.zbuf);
-        w1.part1 = (unsigned long long *)(base + L.part1);
-        w1.zbuf1 = (unsigned long long *)(base + L.zbuf1);
-        w1.scratch = (float *)(base + L.scratch);
-        const char *pe = getenv("PHX_PROF");
-        w1.prof = (pe && atoi(pe) >= 1) ? (unsigned long long *)(base + L.prof) : nullptr;
-        w1.prof_level = pe ? atoi(pe) : 0;
-        w1.wimg = (const float *)(base + L.wimg);
-        const size_t lds = lds_bytes_fwd3(d1);
-        // header + set 0 are contiguous: one fill -- unless the caller vouches for the workspace (ws_keep) and the batch is
-        // one launch (see adj3_run)
-        const bool fill = !(o->ws_keep && chunk >= B);
-        if (fill && hipMemsetAsync(w1.cnt, 0, L.part - L.cnt + L.xbytes, st) != hipSuccess) return PHX_ERR_LAUNCH;
-        const dim3 grid1(d1.TG * d1.G), blk1(64 * d1.NW);
-        if (p->wimg) w1.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
-        else
-            hipLaunchKernelGGL(k1_pack_images, dim3(d1.nblk), dim3(256), 0, st, to_net(p), (float *)w1.wimg, d1.HT, 1, p->H,
-                               blk_floats_ch(d1.HT, p->H));
-        auto launch = [&](auto kern) -> int {
-            const void *fn = reinterpret_cast<const void *>(kern);
-            if (!set_lds_fn(fn, lds)) return PHX_ERR_LAUNCH;
-            // the workgroups of a launch wait for each other's rows: refuse a grid the device cannot hold at once
-            if (!fits_resident(fn, 64 * d1.NW, lds, d1.TG * d1.G)) return PHX_ERR_LAUNCH;
-            ev_begin(st);
-            const hipError_t lerr = launch_persistent(fn, grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t, sol, status, nfe, nsteps);
-            ev_end(st);
-            return lerr == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
-        };
-        // HALF: the last hidden tile has at most 8 live rows (H <= 40 with three tiles; rho16 in phx_mfma_v3common.inc)
-        const char *eh = getenv("PHX_V3_HALF");   // diagnostic: 0 = full last tile also where half of it is padding
-        const bool half = p->H <= 16 * (d1.HT - 1) + 8 && !(eh && eh[0] == '0');
-        const bool split = v3_split_parts(d1.TG, d1.NW, d1.TPW, d1.ntg) > 1;   // small batch: the waves of a tile split its blocks
-        const int lrc = split ? (half ? launch(k1_solve_fwd3<3, 256, true, true>) : launch(k1_solve_fwd3<3, 256, false, true>))
-                              : (half ? launch(k1_solve_fwd3<3, 256, true, false>) : launch(k1_solve_fwd3<3, 256, false, false>));
-        if (lrc != PHX_OK) return lrc;
-        if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
-    }
-    return PHX_OK;
-}
-
 }  // namespace phxh

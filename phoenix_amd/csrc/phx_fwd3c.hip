@@ -37,7 +37,7 @@ int env_int(const char *name, int dflt)
 // keeps their partial sums in registers); all chunks LDS resident when they fit, else one re-staged slot.  Cost: the
 // per-wave MFMA work first, then the exchange volume (members per group).  A plan of ONE slot per wave whose workgroups
 // leave half the chip idle takes HALF-BLOCK gene tiles (hb: twice the workgroups, half the sweep work each).
-bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out, int *nbt_out)
+bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
 {
     const int cus = num_cus();
     if (cus <= 0 || fwd3c_disabled() || method != PHX_DOPRI5 || H <= 48 || H > 256) return false;
@@ -48,7 +48,6 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out, in
     const int fhb = env_int("PHX_V3C_HB", -1);
     long long best_cost = -1;
     D1 best{};
-    int best_nbt = 0;
     for (int NW = 4; NW >= 1; NW >>= 1)
         for (int TPW = 1; TPW <= 8; TPW <<= 1) {
             if (ftpw > 0 && TPW != ftpw) continue;
@@ -70,6 +69,9 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out, in
                 }
             }
             const int Bt = 16 * ntg;
+            // the controllers step one trajectory per thread (k1_solve_fwd3c: `tid < Bt`): a group of more trajectories
+            // than the workgroup has threads (eight-tile waves, more than 16 tiles) would leave the rest unsolved
+            if (Bt > 64 * NW) continue;
             const bool helpers = ntg < slots;
             if (control == PHX_CTRL_SHARED && TG != 1) continue;
             const size_t cb = ctlf3c_bytes(Bt, ntg);
@@ -93,15 +95,12 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out, in
                     // groups on all of it) and a group has at most 160 members; +5..+24 % beyond (tools/v3c_check.py hbgrid)
                     const bool hb_fits = nslot == 1 && res && (long long)TG * G * 2 <= cus && cb + HSF_BYTES + 16 + blkbytes * HC <= LDS_BUDGET;
                     best.hb = (hb_fits && fhb != 0 && (fhb == 1 || ((long long)TG * G * ntg <= cus && 2 * nblk <= 160))) ? 1 : 0;
-                    best_nbt = nslot <= 1 ? 1 : 8;   // (unused slots of the eight-slot form cost a scalar branch each)
                     // block split: a tile's gene blocks on the workgroup's spare waves (small batches of multi-block tiles)
                     best.split = 1;
                     if (!best.hb && TPW == 1 && NB > 1 && ntg * NB <= NW && env_int("PHX_V3C_SPLIT", 1) != 0) {
                         const int parts = std::min(NW / ntg, NB);
-                        if (hsf_offset(Bt, ntg) + spf_bytes(ntg, parts) + blkbytes * NB * (res ? HC : 1) <= LDS_BUDGET) {
+                        if (hsf_offset(Bt, ntg) + spf_bytes(ntg, parts) + blkbytes * NB * (res ? HC : 1) <= LDS_BUDGET)
                             best.split = parts;
-                            best_nbt = 1;
-                        }
                     }
                 }
             }
@@ -109,40 +108,25 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out, in
     if (best_cost < 0) return false;
     if (best.hb) best.G = 2 * best.nblk;
     *out = best;
-    if (nbt_out) *nbt_out = best_nbt;
     return true;
 }
 
-int pick_chunk_fwd3c(int N, int H, int B, int T, int control, int method)
-{
-    D1 d1;
-    if (plan_fwd3c(N, H, B, T, control, method, &d1, nullptr)) return B;
-    if (control != PHX_CTRL_PER_TRAJECTORY) return 0;
-    for (int bc = 4096; bc >= 16; bc >>= 1)
-        if (bc < B && plan_fwd3c(N, H, bc, T, control, method, &d1, nullptr)) return bc;
-    return 0;
-}
 
-struct LayoutF3C {
-    size_t total, cnt, part, zbuf, part1, zbuf1, scratch, prof, xbytes, wimg;
-};
-
-LayoutF3C make_layout_f3c(const D1 &d)
+Regions make_layout_f3c(const D1 &d, bool)
 {
-    LayoutF3C L;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Regions L{};
+    Take take;
     const size_t R = (size_t)d.ntg * d.HC * 2 * d.HT * 4 + d.ntg;   // hidden rows of every chunk + norm rows per group
     L.cnt = take(4096);
     L.part = take((size_t)d.TG * d.G * R * 64 * 8);
     L.zbuf = take((size_t)d.TG * R * 64 * 8);
-    L.xbytes = off - L.part;                                 // header + set 0: what a fill covers (phx_mfma_v3common.inc: XSet)
+    L.xbytes = take.off - L.part;                            // header + set 0: what a fill covers (phx_mfma_v3common.inc: XSet)
     L.part1 = take((size_t)d.TG * d.G * R * 64 * 8);         // set 1: cleaned by the launch that works in set 0
     L.zbuf1 = take((size_t)d.TG * R * 64 * 8);
     L.scratch = take((size_t)d.TG * d.G * NVEC_FWD3C * d.ntg * d.NB * 512 * 4);
     L.prof = take((size_t)d.TG * d.G * 16 * 8);
     L.wimg = take((size_t)d.nblk * d.HC * blk_floats_ch(d.HT, d.Hc) * 4);
-    L.total = off;
+    L.total = take.off;
     return L;
 }
 
@@ -153,102 +137,40 @@ size_t lds_bytes_fwd3c(const D1 &d)
                  : (d.split > 1 ? hsf_offset(d.Bt, d.ntg) + spf_bytes(d.ntg, d.split) : ctlf3c_bytes(d.Bt, d.ntg)));
 }
 
+const void *prepare_fwd3c(SolveArgs &a, const phx_params *p, hipStream_t st)
+{
+    const D1 &d = a.d;
+    // the chunk images of this kernel family (three-tile chunks) are not the caller's phx_params.wimg format for H > 48
+    // (one eight-tile chunk / seven-tile 100-row chunks): packed per launch from the parameter tensors
+    hipLaunchKernelGGL(k1_pack_images, dim3(d.nblk * d.HC), dim3(256), 0, st, to_net(p), (float *)a.w.wimg, d.HT, d.HC, d.Hc,
+                       blk_floats_ch(d.HT, d.Hc));
+    a.lds = lds_bytes_fwd3c(d);
+    // (tile, block) slots per wave the kernel is built for (unused slots of the eight-slot form cost a scalar branch each)
+    const int nbt = d.TPW * d.NB <= 1 || d.split > 1 ? 1 : 8;
+    const bool half = d.Hc <= 40;   // every chunk's last tile has at most 8 live rows (rho16, phx_mfma_v3common.inc)
+    switch (nbt * 2 + (half ? 1 : 0) + (d.hb ? 32 : 0)) {
+    case 35: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, true>);
+    case 34: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, false, true>);
+    case 3: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, false>);
+    case 2: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, false, false>);
+    case 17: return reinterpret_cast<const void *>(k1_solve_fwd3c<8, true, false>);
+    default: return reinterpret_cast<const void *>(k1_solve_fwd3c<8, false, false>);
+    }
+}
+
+hipError_t launch_fwd3c(const void *fn, const SolveArgs &a, hipStream_t st)
+{
+    return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.y0, a.t, a.sol,
+                             a.status, a.nfe, a.nsteps);
+}
+
 }  // namespace
 
 namespace phxh {
-
-int fwd3c_chunk(int N, int H, int B, int T, int control, int method) { return pick_chunk_fwd3c(N, H, B, T, control, method); }
-
-size_t fwd3c_workspace_bytes(int N, int H, int B, int T)
+const Backend &fwd3c_backend()
 {
-    size_t need = 0;
-    for (int ctl = 0; ctl < 2; ++ctl) {
-        D1 d1;
-        const int bc = pick_chunk_fwd3c(N, H, B, T, ctl, PHX_DOPRI5);
-        if (bc > 0 && plan_fwd3c(N, H, bc, T, ctl, PHX_DOPRI5, &d1, nullptr)) need = std::max(need, make_layout_f3c(d1).total);
-    }
-    return need;
+    static const Backend b = {4, true, false, true,
+                                    plan_fwd3c, make_layout_f3c, plan6_chunked, prepare_fwd3c, launch_fwd3c, nullptr};
+    return b;
 }
-
-int fwd3c_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6)
-{
-    D1 d1;
-    if (!plan_fwd3c(N, H, B, T, control, PHX_DOPRI5, &d1, nullptr)) return PHX_ERR_BAD_ARG;
-    *offset = make_layout_f3c(d1).prof;
-    *n_workgroups = d1.TG * d1.G;
-    if (plan6) { plan6[0] = d1.NW; plan6[1] = d1.TPW; plan6[2] = d1.NB; plan6[3] = d1.G; plan6[4] = d1.TG; plan6[5] = d1.HC * 10 + d1.res + 2 * d1.hb + (d1.split > 1 ? 4 : 0); }
-    return PHX_OK;
-}
-
-int fwd3c_run(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
-              float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes,
-              hipStream_t st)
-{
-    SolveCfg cfg;
-    cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
-    cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
-    cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
-    const int chunk = pick_chunk_fwd3c(p->N, p->H, B, T, o->control, o->method);
-    if (chunk <= 0) return PHX_ERR_BAD_ARG;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        D1 d1;
-        int nbt = 0;
-        const int bc = std::min(chunk, B - b0);
-        if (!plan_fwd3c(p->N, p->H, bc, T, o->control, o->method, &d1, &nbt)) return PHX_ERR_BAD_ARG;
-        d1.BN = (long long)B * p->N;   // time stride of the caller's [T,B,N] arrays
-        const float *y0 = y0_all + (long long)b0 * p->N;
-        const double *t = !o->t_per_sample ? t_all   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
-                          : reinterpret_cast<const double *>(reinterpret_cast<const char *>(t_all) +
-                                                             (size_t)b0 * T * (o->t_is_f32 == 2 ? 4 : 8));
-        float *sol = sol_all + (long long)b0 * p->N;
-        int *status = status_all + b0, *nfe = nfe_all + b0, *nsteps = nsteps_all + b0;
-        const LayoutF3C L = make_layout_f3c(d1);
-        if (workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
-        char *base = (char *)workspace;
-        W1 w1{};
-        w1.cnt = (unsigned long long *)(base + L.cnt);
-        w1.abort_flag = (unsigned int *)(base + L.cnt + 2048);
-        w1.part = (unsigned long long *)(base + L.part);
-        w1.zbuf = (unsigned long long *)(base + L.zbuf);
-        w1.part1 = (unsigned long long *)(base + L.part1);
-        w1.zbuf1 = (unsigned long long *)(base + L.zbuf1);
-        w1.scratch = (float *)(base + L.scratch);
-        const char *pe = getenv("PHX_PROF");
-        w1.prof = (pe && atoi(pe) >= 1) ? (unsigned long long *)(base + L.prof) : nullptr;
-        w1.prof_level = pe ? atoi(pe) : 0;
-        w1.wimg = (const float *)(base + L.wimg);
-        const size_t lds = lds_bytes_fwd3c(d1);
-        const bool fill = !(o->ws_keep && chunk >= B);
-        if (fill && hipMemsetAsync(w1.cnt, 0, L.part - L.cnt + L.xbytes, st) != hipSuccess) return PHX_ERR_LAUNCH;
-        const dim3 grid1(d1.TG * d1.G), blk1(64 * d1.NW);
-        // the chunk images of this kernel family (three-tile chunks) are not the caller's phx_params.wimg format for H > 48
-        // (one eight-tile chunk / seven-tile 100-row chunks): packed per launch from the parameter tensors
-        hipLaunchKernelGGL(k1_pack_images, dim3(d1.nblk * d1.HC), dim3(256), 0, st, to_net(p), (float *)w1.wimg, d1.HT, d1.HC,
-                           d1.Hc, blk_floats_ch(d1.HT, d1.Hc));
-        auto launch = [&](auto kern) -> int {
-            const void *fn = reinterpret_cast<const void *>(kern);
-            if (!set_lds_fn(fn, lds)) return PHX_ERR_LAUNCH;
-            // the workgroups of a launch wait for each other's rows: refuse a grid the device cannot hold at once
-            if (!fits_resident(fn, 64 * d1.NW, lds, d1.TG * d1.G)) return PHX_ERR_LAUNCH;
-            if (b0 == 0) ev_begin(st);   // (ONE event pair around all launches of a batch that runs in several)
-            const hipError_t lerr = launch_persistent(fn, grid1, blk1, lds, st, to_net(p), d1, w1, cfg, y0, t, sol, status, nfe, nsteps);
-            if (b0 + chunk >= B) ev_end(st);
-            return lerr == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
-        };
-        const bool half = d1.Hc <= 40;   // every chunk's last tile has at most 8 live rows (rho16, phx_mfma_v3common.inc)
-        int lrc;
-        switch (nbt * 2 + (half ? 1 : 0) + (d1.hb ? 32 : 0)) {
-        case 35: lrc = launch(k1_solve_fwd3c<1, true, true>); break;
-        case 34: lrc = launch(k1_solve_fwd3c<1, false, true>); break;
-        case 3: lrc = launch(k1_solve_fwd3c<1, true, false>); break;
-        case 2: lrc = launch(k1_solve_fwd3c<1, false, false>); break;
-        case 17: lrc = launch(k1_solve_fwd3c<8, true, false>); break;
-        default: lrc = launch(k1_solve_fwd3c<8, false, false>); break;
-        }
-        if (lrc != PHX_OK) return lrc;
-        if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
-    }
-    return PHX_OK;
-}
-
 }  // namespace phxh

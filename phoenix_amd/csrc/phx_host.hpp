@@ -100,6 +100,14 @@ inline hipError_t launch_persistent(const void *fn, dim3 grid, dim3 block, size_
     if (use_coop()) return hipLaunchCooperativeKernel(fn, grid, block, argv, (unsigned int)lds, st);
     return hipLaunchKernel(fn, grid, block, argv, lds, st);
 }
+// the plain launch of the older persistent kernels (k1_solve_fwd / adj / adj2: never cooperative); `args` must carry the
+// kernel's parameter types exactly
+template <typename... Args>
+inline hipError_t launch_plain(const void *fn, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args)
+{
+    void *argv[] = {(void *)&args...};
+    return hipLaunchKernel(fn, grid, block, argv, lds, st);
+}
 
 // diagnostic: optional HIP events recorded immediately around the next solve kernel (bench.py roofline timing)
 inline thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
@@ -139,51 +147,69 @@ inline bool force_v0()
 
 }  // namespace phxh
 
-// ---- second-generation adjoint kernel (phx_adj2.hip): plain-type entry points used by the C ABI in phx_engine.hip
+// ---- persistent solve kernels (k1_solve_fwd / fwd3 / fwd3c, k1_solve_adj / adj2 / adj3 / adj3c): one description per
+// kernel family, defined by the family's translation unit; phx_engine.hip picks the family and drives its launches
 namespace phxh {
-// trajectories per launch for this shape (B when one launch takes the whole batch), 0: no plan -> caller falls back
-int adj2_chunk(int N, int H, int B, int T, int control);
-size_t adj2_workspace_bytes(int N, int H, int B, int T);   // max over the control modes (0 when unplanned)
-int adj2_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6);
-// runs the whole batch (in chunks when needed); returns a PHX_* status
-int adj2_run(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o, const float *y_saved_all,
-             const float *grad_y_all, float *adj_y0_all, const phx_grads *grads, int *status_all, int *nfe_all,
-             int *nsteps_all, void *workspace, size_t workspace_bytes, hipStream_t st);
-}  // namespace phxh
 
-// ---- third backward kernel (phx_adj3.hip: dopri5, H <= 48, fused sweeps over a 16-vector private state)
-namespace phxh {
-int adj3_chunk(int N, int H, int B, int T, int control, int method);
-size_t adj3_workspace_bytes(int N, int H, int B, int T);   // max over the control modes (0 when unplanned)
-int adj3_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6);
-int adj3_run(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o, const float *y_saved_all,
-             const float *grad_y_all, float *adj_y0_all, const phx_grads *grads, int *status_all, int *nfe_all,
-             int *nsteps_all, void *workspace, size_t workspace_bytes, hipStream_t st);
-}  // namespace phxh
+// workspace layout of one plan: byte offsets of the regions every family draws from (a region a family does not use has
+// zero bytes), in the family's own order
+struct Regions {
+    size_t total, cnt, part, zbuf, part1, zbuf1, scratch, dtheta, prof, wimg, hq;
+    size_t xbytes;      // bytes from `part` on that a fill zeroes together with the header [cnt, part)
+    long long pp;       // backward: floats per gradient partial
+    int nparts;         // backward: partials the gradient reduce sums
+};
 
-// ---- third-generation forward solve (phx_fwd3.hip: dopri5, H <= 48)
-namespace phxh {
-int fwd3_chunk(int N, int H, int B, int T, int control, int method);
-size_t fwd3_workspace_bytes(int N, int H, int B, int T);
-int fwd3_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6);
-int fwd3_run(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
-             float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes,
-             hipStream_t st);
-}  // namespace phxh
+// one launch: the arguments the solve kernels take, pointers already offset to the launch's rows
+struct SolveArgs {
+    Net net;
+    D1 d;
+    W1 w;
+    SolveCfg cfg;
+    size_t lds;
+    const double *t;
+    const float *y0, *y_saved, *grad_y;   // forward: y0; backward: y_saved, grad_y
+    float *sol, *adj_y0;
+    int *status, *nfe, *nsteps;
+    int grads;            // backward: 1 = parameter gradients wanted
+    long long PP;         // backward: Regions::pp
+};
 
-// ---- third-generation kernels for wide hidden layers (phx_fwd3c.hip / phx_adj3c.hip: dopri5, 48 < H <= 256, hidden chunks
-// of <= 48 rows)
-namespace phxh {
-int fwd3c_chunk(int N, int H, int B, int T, int control, int method);
-size_t fwd3c_workspace_bytes(int N, int H, int B, int T);
-int fwd3c_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6);
-int fwd3c_run(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
-              float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes,
-              hipStream_t st);
-int adj3c_chunk(int N, int H, int B, int T, int control, int method);
-size_t adj3c_workspace_bytes(int N, int H, int B, int T);
-int adj3c_profile_region(int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups, int *plan6);
-int adj3c_run(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o, const float *y_saved_all,
-              const float *grad_y_all, float *adj_y0_all, const phx_grads *grads, int *status_all, int *nfe_all,
-              int *nsteps_all, void *workspace, size_t workspace_bytes, hipStream_t st);
+struct Backend {
+    int id;                    // kernel generation phx_debug_{forward,adjoint}_kernel_m report (1 .. 4)
+    bool cleans_idle_set;      // the kernel cleans its idle exchange set: ws_keep may skip the fill of a one-launch batch
+    bool zero_dtheta_always;   // gradient partials are zeroed before every launch, else only when T < 2 (nobody steps)
+    bool prof_levels;          // PHX_PROF=<level >= 1> turns the timers on; else only a value that starts with '1'
+    bool (*plan)(int N, int H, int B, int T, int control, int method, D1 *out);
+    Regions (*layout)(const D1 &d, bool grads);
+    int (*plan6)(const D1 &d);   // last entry of phx_debug_profile_region's plan
+    // the images (packed into a.w.wimg unless the caller's serve), a.lds and the kernel; null: no kernel for this plan
+    const void *(*prepare)(SolveArgs &a, const phx_params *p, hipStream_t st);
+    hipError_t (*launch)(const void *fn, const SolveArgs &a, hipStream_t st);
+    // backward: sums `npart` partials into the caller's gradients; false on a launch error
+    bool (*reduce)(const SolveArgs &a, int npart, const phx_grads *g, int overwrite, hipStream_t st);
+};
+
+// the layouts' allocator: regions 256-byte aligned, in the order they are taken
+struct Take {
+    size_t off = 0;
+    size_t operator()(size_t bytes)
+    {
+        const size_t o = off;
+        off = align_up(off + bytes, 256);
+        return o;
+    }
+};
+
+// plan[5] of phx_debug_profile_region: the hidden tiles, or for the hidden-chunked kernels HC*10 + res + 2 hb + 4 split
+inline int plan6_ht(const D1 &d) { return d.HT; }
+inline int plan6_chunked(const D1 &d) { return d.HC * 10 + d.res + 2 * d.hb + (d.split > 1 ? 4 : 0); }
+
+// (functions: a host object at namespace scope that holds host function pointers breaks the device link)
+const Backend &fwd3_backend();
+const Backend &fwd3c_backend();
+const Backend &adj2_backend();
+const Backend &adj3_backend();
+const Backend &adj3c_backend();
+
 }  // namespace phxh
