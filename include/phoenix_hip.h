@@ -149,6 +149,29 @@ int phx_odeint_adjoint_backward(const phx_params *p, const double *t, int B, int
                                 int *status, int *nfe, int *nsteps, void *workspace,
                                 size_t workspace_bytes, void *stream);
 
+/* options={"step_size": h} of the fixed-grid methods (FixedGridODESolver, solvers.py:36-103): phx_odeint with sub-steps.
+ * Euler / midpoint / rk4 step along ONE grid per trajectory, g_k = k * h + t[0] for k < ceil((t[T-1] - t[0]) / h + 1),
+ * the last point set to t[T-1], formed in the dtype of the caller's t (opts->t_is_f32); output j is the state at the
+ * grid point equal to t[j], else the linear interpolant of the step that passes t[j].  Intermediate states stay on chip.
+ * nsteps [B] = grid steps taken, nfe = stages * nsteps.  step_size <= 0 (or not finite), or method dopri5: exactly
+ * phx_odeint.  opts->max_num_steps > 0 is a budget of grid steps per trajectory (PHX_ERR_MAX_STEPS in status).
+ * PHX_ERR_BAD_ARG when no kernel with the sub-step loop plans the shape (opts->calls > 1, or a shape only the VALU
+ * engine serves, H > 256: never one step per interval in silence).  Same workspace as phx_odeint. */
+int phx_odeint_stepped(const phx_params *p, const float *y0, const double *t, int B, int T,
+                       const phx_solve_opts *opts, float *sol, int *status, int *nfe, int *nsteps,
+                       void *workspace, size_t workspace_bytes, void *stream, double step_size);
+
+/* ... and the backward solve under it (adjoint.py:137-154 calling odeint per interval with adjoint_options): every
+ * interval [t[i], t[i-1]] has its own grid anchored at t[i] whose last step ends on t[i-1] (no interpolation), one set
+ * of quadrature weights per sub-step, the jump after the last one.  nsteps / nfe add up the intervals.  step_size <= 0
+ * or dopri5: exactly phx_odeint_adjoint_backward.  opts->max_num_steps > 0 is a budget of grid steps per interval.
+ * k1_solve_adj2 and k1_solve_adj have the loop; PHX_ERR_BAD_ARG for a shape only the VALU engine serves (H > 256). */
+int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t, int B, int T,
+                                        const phx_solve_opts *opts, const float *y_saved,
+                                        const float *grad_y, float *adj_y0, const phx_grads *grads,
+                                        int *status, int *nfe, int *nsteps, void *workspace,
+                                        size_t workspace_bytes, void *stream, double step_size);
+
 /* prior_grad = X[K,N] @ P[N,N] with the prior matrix P in CSC form
  * (colptr [N+1], rowidx/vals [nnz], rows ascending inside a column).  Replaces the reference's dense
  * `torch.matmul(batch_for_prior, prior_mat)` (train_insilico.py:207-211) and the 0.5 GB dense matrix that
@@ -221,6 +244,8 @@ int phx_debug_adjoint_kernel_m(int N, int H, int B, int T, int control, int meth
  * 3 = k1_solve_fwd3 (MFMA, dopri5 with H <= 48), 4 = k1_solve_fwd3c (its hidden-chunked form, 48 < H <= 256); the
  * adjoint query above likewise returns 4 for k1_solve_adj3c. */
 int phx_debug_forward_kernel_m(int N, int H, int B, int T, int control, int method);
+/* Both *_m queries: `method | 0x100` asks for the kernel of the stepped entry points (phx_odeint_stepped, ...); 0 then
+ * means that no kernel with the sub-step loop plans the shape and the call returns PHX_ERR_BAD_ARG. */
 /* Diagnostic only: how many launches of that solve kernel one call with this batch makes (a batch that does not fit one
  * residency is walked in chunks: e.g. 256 B-cell trajectories = two launches of k1_solve_adj3c).  op = PHX_OP_ODEINT or
  * PHX_OP_ADJOINT; 0 when no plan exists.  bench.py multiplies per-launch profile figures with it. */

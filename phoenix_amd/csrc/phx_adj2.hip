@@ -71,6 +71,7 @@ bool plan_adj2(int N, int H, int B, int T, int control, int /* method: any */, D
     // Narrow hidden layer exchanged among many gene tiles (the breast-cancer shape: H = 40, 59 members per group): the
     // first-generation kernel (one wave per trajectory tile doing both halves of the augmented state: twice the MFMA
     // work per gene-block visit) is still the faster one there -- 0.73 against 0.90 ms.  PHX_ADJ=v2 forces this kernel.
+    // (with a step size too: k1_solve_adj has the sub-step loop as well)
     if (best.HT == 3 && best.G > 32 && !adj2_forced()) return false;
     *out = best;
     return true;
@@ -144,7 +145,7 @@ bool reduce_adj2(const SolveArgs &a, int npart, const phx_grads *g, int overwrit
 namespace phxh {
 const Backend &adj2_backend()
 {
-    static const Backend b = {2, false, true, false, plan_adj2, make_layout2, plan6_ht, prepare_adj2, launch_adj2, reduce_adj2};
+    static const Backend b = {2, false, true, false, plan_adj2, make_layout2, plan6_ht, prepare_adj2, launch_adj2, reduce_adj2, true};
     return b;
 }
 }  // namespace phxh

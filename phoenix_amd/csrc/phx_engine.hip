@@ -968,13 +968,13 @@ bool reduce_v1(const SolveArgs &a, int npart, const phx_grads *g, int overwrite,
 const Backend &v1_fwd_backend()
 {
     static const Backend b = {1, false, false, false,
-                                    plan_v1_fwd, layout_v1_fwd, plan6_ht, prepare_v1_fwd, launch_v1_fwd, nullptr};
+                                    plan_v1_fwd, layout_v1_fwd, plan6_ht, prepare_v1_fwd, launch_v1_fwd, nullptr, true};
     return b;
 }
 const Backend &v1_adj_backend()
 {
     static const Backend b = {1, false, false, false,
-                                    plan_v1_adj, layout_v1_adj, plan6_ht, prepare_v1_adj, launch_v1_adj, reduce_v1};
+                                    plan_v1_adj, layout_v1_adj, plan6_ht, prepare_v1_adj, launch_v1_adj, reduce_v1, true};
     return b;
 }
 
@@ -1007,10 +1007,12 @@ struct Pick {
 };
 
 // the first kernel of the direction that plans the batch; whole: only a plan of the whole batch in one launch counts
-Pick first_backend(int op, int N, int H, int B, int T, int control, int method, bool whole = false)
+// stepped: only a kernel whose fixed-grid arm takes the sub-steps of options["step_size"] counts
+Pick first_backend(int op, int N, int H, int B, int T, int control, int method, bool whole = false, bool stepped = false)
 {
     for (const Backend *const *b = backends(op); *b; ++b) {
         D1 d;
+        if (stepped && !(*b)->substeps) continue;
         const int chunk = !whole ? pick_chunk(**b, N, H, B, T, control, method)
                                  : (*b)->plan(N, H, B, T, control, method, &d) ? B : 0;
         if (chunk > 0) return {*b, chunk};
@@ -1024,6 +1026,7 @@ SolveCfg solve_cfg(const phx_solve_opts *o)
     cfg.method = o->method; cfg.control = o->control; cfg.t_per_sample = o->t_per_sample; cfg.t_is_f32 = o->t_is_f32;
     cfg.rtol = (float)o->rtol; cfg.atol = (float)o->atol;
     cfg.max_steps = o->max_num_steps > 0 ? o->max_num_steps : 2147483647LL;
+    cfg.step = 0.0;
     return cfg;
 }
 
@@ -1041,6 +1044,8 @@ struct SolveCall {
     void *workspace;
     size_t workspace_bytes;
     hipStream_t st;
+    double step = 0.0;   // SolveCfg::step
+    int control = -1;    // >= 0: the step control the launches are planned and run with instead of o->control
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1067,6 +1072,8 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
     SolveArgs a{};
     a.net = to_net(p);
     a.cfg = solve_cfg(o);
+    a.cfg.step = c.step;
+    if (c.control >= 0) a.cfg.control = c.control;
     a.grads = c.grads ? 1 : 0;
     const char *pe = getenv("PHX_PROF");   // segment timers (Backend::prof_levels); 2, 3: finer timers of some kernels
     const int plevel = pe ? atoi(pe) : 0;
@@ -1126,7 +1133,8 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
 int run_solve(const Pick &k, const SolveCall &c)
 {
     const Backend &be = *k.be;
-    return run_solve(be, k.chunk, [&](int bc, D1 *d) { return be.plan(c.p->N, c.p->H, bc, c.T, c.o->control, c.o->method, d); },
+    const int control = c.control >= 0 ? c.control : c.o->control;
+    return run_solve(be, k.chunk, [&](int bc, D1 *d) { return be.plan(c.p->N, c.p->H, bc, c.T, control, c.o->method, d); },
                      c);
 }
 
@@ -1585,12 +1593,21 @@ int phx_debug_adjoint_kernel(int N, int H, int B, int T, int control)
 
 int phx_debug_adjoint_kernel_m(int N, int H, int B, int T, int control, int method)
 {
+    if (method & 0x100)   // the kernel of a solve with a step size (planned per trajectory); 0: none, the solve is refused
+        return [&] {
+            const Pick s = first_backend(PHX_OP_ADJOINT, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
+            return s.be ? s.be->id : 0;
+        }();
     const Pick k = first_backend(PHX_OP_ADJOINT, N, H, B, T, control, method);
     return k.be ? k.be->id : 0;
 }
 
 int phx_debug_forward_kernel_m(int N, int H, int B, int T, int control, int method)
 {
+    if (method & 0x100) {   // as in phx_debug_adjoint_kernel_m
+        const Pick s = first_backend(PHX_OP_ODEINT, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
+        return s.be ? s.be->id : 0;
+    }
     const Pick k = first_backend(PHX_OP_ODEINT, N, H, B, T, control, method);
     return k.be ? k.be->id : 0;
 }
@@ -1805,14 +1822,38 @@ int phx_odeint(const phx_params *p, const float *y0_all, const double *t_all, in
                float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes,
                void *stream)
 {
+    return phx_odeint_stepped(p, y0_all, t_all, B, T, o, sol_all, status_all, nfe_all, nsteps_all, workspace, workspace_bytes,
+                              stream, 0.0);
+}
+
+// a step size counts for a fixed-grid method only, and only a positive finite one
+static bool is_stepped(const phx_solve_opts *o, double step_size)
+{
+    return o->method != PHX_DOPRI5 && step_size > 0.0 && step_size <= 1.7976931348623157e308;
+}
+
+int phx_odeint_stepped(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
+                       float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
+                       size_t workspace_bytes, void *stream, double step_size)
+{
     if (bad_params(p) || !y0_all || !t_all || !o || !sol_all || !status_all || !nfe_all || !nsteps_all || B <= 0 ||
         T < 1 || !workspace)
         return PHX_ERR_BAD_ARG;
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
-                      workspace, workspace_bytes, st};
+    SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
+                workspace, workspace_bytes, st};
+    if (is_stepped(o, step_size)) {
+        // Sub-steps inside the intervals of t: the persistent kernels that have the loop, or none (no kernel takes one
+        // step per interval when a step size was asked for).  A fixed grid has no step controller, so its batch is always
+        // planned per trajectory: any batch size goes in chunks.
+        if (o->calls > 1) return PHX_ERR_BAD_ARG;
+        c.step = step_size;
+        c.control = PHX_CTRL_PER_TRAJECTORY;
+        const Pick k = first_backend(PHX_OP_ODEINT, p->N, p->H, B, T, c.control, o->method, false, true);
+        return k.be ? run_solve(k, c) : (int)PHX_ERR_BAD_ARG;
+    }
     // several calls in one batch (analysis callers): every call keeps its own shared controller, a launch takes as many
     // calls as there are batch groups to run them (first-generation kernel only)
     if (o->calls > 1) {
@@ -1845,6 +1886,15 @@ int phx_odeint_adjoint_backward(const phx_params *p, const double *t_all, int B,
                                 const phx_grads *grads, int *status_all, int *nfe_all, int *nsteps_all,
                                 void *workspace, size_t workspace_bytes, void *stream)
 {
+    return phx_odeint_adjoint_backward_stepped(p, t_all, B, T, o, y_saved_all, grad_y_all, adj_y0_all, grads, status_all,
+                                               nfe_all, nsteps_all, workspace, workspace_bytes, stream, 0.0);
+}
+
+int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o,
+                                        const float *y_saved_all, const float *grad_y_all, float *adj_y0_all,
+                                        const phx_grads *grads, int *status_all, int *nfe_all, int *nsteps_all,
+                                        void *workspace, size_t workspace_bytes, void *stream, double step_size)
+{
     if (bad_params(p) || !t_all || !o || !y_saved_all || !grad_y_all || !adj_y0_all || !status_all || !nfe_all ||
         !nsteps_all || B <= 0 || T < 1 || !workspace)
         return PHX_ERR_BAD_ARG;
@@ -1853,6 +1903,14 @@ int phx_odeint_adjoint_backward(const phx_params *p, const double *t_all, int B,
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
+    if (is_stepped(o, step_size)) {   // as in phx_odeint_stepped
+        SolveCall c{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all, nfe_all, nsteps_all,
+                    grads, workspace, workspace_bytes, st};
+        c.step = step_size;
+        c.control = PHX_CTRL_PER_TRAJECTORY;
+        const Pick k = first_backend(PHX_OP_ADJOINT, p->N, p->H, B, T, c.control, o->method, false, true);
+        return k.be ? run_solve(k, c) : (int)PHX_ERR_BAD_ARG;
+    }
     const Pick k = first_backend(PHX_OP_ADJOINT, p->N, p->H, B, T, o->control, o->method);
     if (k.be)
         return run_solve(k, SolveCall{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all,

@@ -188,6 +188,7 @@ struct Backend {
     hipError_t (*launch)(const void *fn, const SolveArgs &a, hipStream_t st);
     // backward: sums `npart` partials into the caller's gradients; false on a launch error
     bool (*reduce)(const SolveArgs &a, int npart, const phx_grads *g, int overwrite, hipStream_t st);
+    bool substeps = false;     // the fixed-grid arm takes the sub-steps of options["step_size"] (SolveCfg::step)
 };
 
 // the layouts' allocator: regions 256-byte aligned, in the order they are taken

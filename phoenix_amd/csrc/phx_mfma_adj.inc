@@ -142,7 +142,9 @@ __global__ __launch_bounds__(MAXT) void k1_solve_adj(Net net, D1 d, W1 w, SolveC
         __syncthreads();
         return c.misc[0];
     };
+    const bool stepped = cfg.method != PHX_DOPRI5 && cfg.step > 0.0;   // options["step_size"]: see k1_solve_adj2
     auto dt_rev = [&](int lb, int iv) -> float {   // reversed pair (-t_i, -t_{i-1}) of the fixed grid
+        if (stepped) return c.dtf[lb];             // ... or the running step of the interval's own grid
         const int b = grp * Bt + lb;
         const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
         const double sg = (double)c.sgn[lb];
@@ -898,6 +900,104 @@ __global__ __launch_bounds__(MAXT) void k1_solve_adj(Net net, D1 d, W1 w, SolveC
 
     float nv[2];
     for (int iv = T - 1; iv >= 1; --iv) {
+        if (stepped) {
+            // ------------------------------------------------------------ fixed grid with a step size (adjoint.py:137-154
+            // calls odeint per interval): the interval's own grid anchored at its start, one set of quadrature weights per
+            // step, the jump after the last one.  out_lo = steps of the grid, out_hi = steps taken, rk_t0 / rk_t1 = the
+            // running step; a trajectory whose grid has ended is masked by `done` until the next interval.
+            const int S = fixed_nstages(cfg.method);
+            const bool tf32 = cfg.t_is_f32 != 0;
+            __syncthreads();
+            for (int lb = tid; lb < Bt; lb += blockDim.x) {
+                const int b = grp * Bt + lb;
+                c.dtf[lb] = 0.f;
+                if (b >= B || c.st[lb] != PHX_OK) { c.done[lb] = 1; continue; }
+                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                const double sg = (double)c.sgn[lb];
+                const int n = step_grid_steps(-sg * tb[iv], -sg * tb[iv - 1], cfg.step, tf32);
+                c.done[lb] = 0;
+                c.out_lo[lb] = n; c.out_hi[lb] = 0;
+                c.rk_t1[lb] = -sg * tb[iv];
+                c.fin[lb] = 0;
+                if ((long long)n > cfg.max_steps) { c.st[lb] = PHX_ERR_MAX_STEPS; c.done[lb] = 1; }   // budget per interval
+            }
+            int active = count_active();
+            while (active > 0 && !x.aborted) {
+                for (int lb = tid; lb < Bt; lb += blockDim.x) {
+                    if (c.done[lb]) continue;
+                    const TimeRow tb = trowT(t, T, cfg, shared ? 0 : grp * Bt + lb);
+                    const double sg = (double)c.sgn[lb];
+                    const int k = c.out_hi[lb], n = c.out_lo[lb];
+                    const double g0 = c.rk_t1[lb];
+                    const double g1 = step_grid_at(-sg * tb[iv], -sg * tb[iv - 1], cfg.step, tf32, n, k + 1);
+                    c.rk_t0[lb] = g0; c.rk_t1[lb] = g1;
+                    c.dtf[lb] = tf32 ? ((float)g1 - (float)g0) : (float)(g1 - g0);
+                    c.out_hi[lb] = k + 1;
+                    c.fin[lb] = (k + 1 >= n) ? 1 : 0;
+                }
+                __syncthreads();
+                for (int st = 0; st < S; ++st) eval_aug(3, st, iv, st, 0);
+                __syncthreads();
+                for (int lb = tid; lb < Bt; lb += blockDim.x) {
+                    const bool act = !c.done[lb];
+                    const float dtl = c.dtf[lb];
+                    for (int j = 0; j < 8; ++j)
+                        wq[lb * 8 + j] = (act && j < S) ? c.sgn[lb] * fixed_weight(cfg.method, j, dtl) : 0.f;
+                    if (act) { c.nsteps[lb] += 1; c.nfe[lb] += S; }
+                }
+                __syncthreads();
+                if (want_grads) phaseG(S);
+                for (int s = 0; s < d.TPW; ++s) {
+                    const int ttl = wv * d.TPW + s;
+                    if (ttl >= ntg) continue;   // helper wave: no trajectory tile of its own, it only serves the exchange
+                    const int lb = ttl * 16 + li;
+                    const int b = grp * Bt + lb;
+                    const float dtl = c.dtf[lb];
+                    const bool act = !c.done[lb];
+                    const int fin = c.fin[lb];
+                    if (!__any(act)) continue;
+                    for (int bl = 0; bl < nbl; ++bl) {
+                        float x0[2][8], k0[2][8], k1[2][8], k2[2][8], k3[2][8], gy8[8], ys8[8];
+                        {   // jump data of the trajectories whose grid ends with this step (adjoint.py:152-154)
+                            const long long ro = (long long)(iv - 1) * d.BN + (long long)b * N;
+                            const int g0 = (blk0 + bl) * 32 + gmap(lq, 0);
+                            row_load8(grad_y, ro, g0, N, (b < B) && fin == 1, 0.f, gy8);
+                            row_load8(y_saved, ro, g0, N, (b < B) && fin == 1, 0.5f, ys8);
+                        }
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {   // 0: y, 1: a -- the step's own combination of either half
+                            const int K = h ? A_KA : A_KY;
+                            load8(tptr(h ? A_A0 : A_Y0, ttl, bl), x0[h]);
+                            load8(tptr(K, ttl, bl), k0[h]);
+                            if (S >= 2) load8(tptr(K + 1, ttl, bl), k1[h]);
+                            if (S >= 4) { load8(tptr(K + 2, ttl, bl), k2[h]); load8(tptr(K + 3, ttl, bl), k3[h]); }
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                float x1;
+                                if (cfg.method == PHX_EULER) x1 = x0[h][j] + dtl * k0[h][j];
+                                else if (cfg.method == PHX_MIDPOINT) x1 = x0[h][j] + dtl * k1[h][j];
+                                else x1 = x0[h][j] + (((k0[h][j] + 3.0f * (k1[h][j] + k2[h][j])) + k3[h][j]) * dtl) * 0.125f;
+                                x0[h][j] = x1;
+                            }
+                        }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j)
+                            if (fin == 1) { x0[0][j] = ys8[j]; x0[1][j] += gy8[j]; }
+                        if (act) {
+                            store8(tptr(A_A0, ttl, bl), x0[1]);
+                            store8(tptr(A_Y0, ttl, bl), x0[0]);
+                        }
+                    }
+                }
+                __syncthreads();
+                if (tid < Bt && !c.done[tid] && c.fin[tid]) {
+                    c.done[tid] = 1;
+                    for (int j = 0; j < 8; ++j) wq[tid * 8 + j] = 0.f;
+                }
+                active = count_active();
+            }
+            continue;
+        }
         if (cfg.method != PHX_DOPRI5) {
             // ------------------------------------------------------------ fixed grid: one reversed step
             const int S = fixed_nstages(cfg.method);

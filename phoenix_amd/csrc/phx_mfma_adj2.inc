@@ -394,7 +394,12 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
         while (wall_clock64() - t0 < (unsigned long long)stagger_ticks) __builtin_amdgcn_s_sleep(8);
     }
 
+    // options["step_size"]: every interval has its own step grid anchored at its start (adjoint.py:137-154 calls odeint
+    // per interval); c.nsiv = steps taken in the interval, c.rk_t0 / rk_t1 / dtf = the running step; cfg.max_steps is a
+    // budget of grid steps per interval, as it is per interval for dopri5
+    const bool stepped = cfg.method != PHX_DOPRI5 && cfg.step > 0.0;
     auto dt_rev = [&](int i, int b, int iv) -> float {   // reversed pair (-t_i, -t_{i-1}) of the fixed grid
+        if (stepped) return c.dtf[i];
         const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
         const double sg = (double)c.sgn[i];
         const double u0 = -sg * tb[iv], u1 = -sg * tb[iv - 1];
@@ -1248,6 +1253,30 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
             }
             wave_lds_sync();
         }
+        if (stepped) {
+            for (int s = 0; s < nts; ++s) {
+                const int i = s * 16 + li;
+                const int b = grp * Bt + (pr * TPW + s) * 16 + li;
+                if (lq == 0) {
+                    if (b >= B || c.st[i] != PHX_OK) c.done[i] = 1;
+                    else {
+                        const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                        const double sg = (double)c.sgn[i];
+                        const double u0 = -sg * tb[iv], u1 = -sg * tb[iv - 1];
+                        const bool tf32 = cfg.t_is_f32 != 0;
+                        const int n = step_grid_steps(u0, u1, cfg.step, tf32);
+                        const double g1 = step_grid_at(u0, u1, cfg.step, tf32, n, 1);
+                        c.done[i] = 0;
+                        if ((long long)n > cfg.max_steps) { c.st[i] = PHX_ERR_MAX_STEPS; c.done[i] = 1; }
+                        c.nsiv[i] = 0;
+                        c.rk_t0[i] = u0; c.rk_t1[i] = g1;
+                        c.dtf[i] = tf32 ? ((float)g1 - (float)u0) : (float)(g1 - u0);
+                        c.accept[i] = 0; c.fin[i] = 0;
+                    }
+                }
+            }
+            wave_lds_sync();
+        }
         int ph = 0;
         bool more = true;
         while (more) {
@@ -1298,7 +1327,16 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
                     if (lq == 0) {
                         for (int j = 0; j < 8; ++j)
                             c.wq[i * 8 + j] = (act && j < S) ? c.sgn[i] * fixed_weight(cfg.method, j, dtl) : 0.f;
-                        if (act) { c.nsteps[i] += 1; c.nfe[i] += S; c.accept[i] = 1; c.fin[i] = 1; }
+                        if (act) {   // (sub-steps: the interval ends, and the jump happens, with the last step of its grid)
+                            c.nsteps[i] += 1; c.nfe[i] += S; c.accept[i] = 1;
+                            int fin = 1;
+                            if (stepped) {
+                                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                                const double sg = (double)c.sgn[i];
+                                fin = c.nsiv[i] + 1 >= step_grid_steps(-sg * tb[iv], -sg * tb[iv - 1], cfg.step, cfg.t_is_f32 != 0);
+                            }
+                            c.fin[i] = fin;
+                        }
                     }
                 }
                 wave_lds_sync();
@@ -1414,6 +1452,20 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
                     if (dopri) {
                         load8(tptr(vXS(side, 6), ttl, bl), x1);
                         load8(tptr(vK(side, 6), ttl, bl), k6);
+                    } else if (side == 1 || __any(adv && fin != 1)) {
+                        // the step's own combination (fixed_grid.py, rk_common.py:96-103); the y-wave needs it only for a
+                        // sub-step inside an interval: at the interval's end its state is replaced by the saved one
+                        float a0[8], f0[8], kq[3][8];
+                        load8(tptr(vX0(side), ttl, bl), a0);
+                        load8(tptr(vK(side, 0), ttl, bl), f0);
+                        if (S >= 2) load8(tptr(vK(side, 1), ttl, bl), kq[0]);
+                        if (S >= 4) { load8(tptr(vK(side, 2), ttl, bl), kq[1]); load8(tptr(vK(side, 3), ttl, bl), kq[2]); }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            if (cfg.method == PHX_EULER) x1[j] = a0[j] + dts * f0[j];
+                            else if (cfg.method == PHX_MIDPOINT) x1[j] = a0[j] + dts * kq[0][j];
+                            else x1[j] = a0[j] + (((f0[j] + 3.0f * (kq[0][j] + kq[1][j])) + kq[2][j]) * dts) * 0.125f;
+                        }
                     }
                     {   // jump data of the trajectories that reach t_{i-1} in this step
                         const long long ro = (long long)(iv - 1) * d.BN + (long long)b * N;
@@ -1427,11 +1479,11 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
                         float aout[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) aout[j] = x1[j];
-                        if (anyfin) {
+                        if (anyfin && dopri) {   // quartic dense output of the adjoint at u_end (interp.py)
                             float a0[8], f0[8], kq[4][8];
                             load8(tptr(vX0(1), ttl, bl), a0);
                             load8(tptr(vK(1, 0), ttl, bl), f0);
-                            if (dopri) {   // quartic dense output of the adjoint at u_end (interp.py)
+                            {
                                 float am[8];
 #pragma unroll
                                 for (int kk = 0; kk < 4; ++kk) load8(tptr(vK(1, 2 + kk), ttl, bl), kq[kk]);   // c_mid2 = 0
@@ -1447,15 +1499,6 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
                                 for (int j = 0; j < 8; ++j) {
                                     am[j] += k6[j] * (dts * DP_CMID[6]);
                                     aout[j] = interp_eval(a0[j], x1[j], a0[j] + am[j], f0[j], k6[j], dts, ix);
-                                }
-                            } else {       // the step's own combination (fixed_grid.py, rk_common.py:96-103)
-                                if (S >= 2) load8(tptr(vK(1, 1), ttl, bl), kq[0]);
-                                if (S >= 4) { load8(tptr(vK(1, 2), ttl, bl), kq[1]); load8(tptr(vK(1, 3), ttl, bl), kq[2]); }
-#pragma unroll
-                                for (int j = 0; j < 8; ++j) {
-                                    if (cfg.method == PHX_EULER) aout[j] = a0[j] + dts * f0[j];
-                                    else if (cfg.method == PHX_MIDPOINT) aout[j] = a0[j] + dts * kq[0][j];
-                                    else aout[j] = a0[j] + (((f0[j] + 3.0f * (kq[0][j] + kq[1][j])) + kq[2][j]) * dts) * 0.125f;
                                 }
                             }
                         }
@@ -1486,7 +1529,33 @@ __global__ __launch_bounds__(128 * NP2) void k1_solve_adj2(Net net, D1 d, W1 w, 
             }
             wave_lds_sync();   // the hq copy above read accept/fin of other lanes before they are reset below
             tm.mark(10);
-            if (!dopri) {
+            if (stepped) {
+                for (int s = 0; s < nts; ++s) {
+                    const int i = s * 16 + li;
+                    const int b = grp * Bt + (pr * TPW + s) * 16 + li;
+                    if (lq == 0) {
+                        if (!c.done[i] && c.fin[i]) {
+                            c.done[i] = 1;
+                            for (int j = 0; j < 8; ++j) c.wq[i * 8 + j] = 0.f;
+                        } else if (!c.done[i]) {   // next step of this interval's grid
+                            const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                            const double sg = (double)c.sgn[i];
+                            const bool tf32 = cfg.t_is_f32 != 0;
+                            const int k = c.nsiv[i] + 1;
+                            const double g0 = c.rk_t1[i];
+                            const double u0 = -sg * tb[iv], u1 = -sg * tb[iv - 1];
+                            const double g1 = step_grid_at(u0, u1, cfg.step, tf32, step_grid_steps(u0, u1, cfg.step, tf32), k + 1);
+                            c.nsiv[i] = k;
+                            c.rk_t0[i] = g0; c.rk_t1[i] = g1;
+                            c.dtf[i] = tf32 ? ((float)g1 - (float)g0) : (float)(g1 - g0);
+                        }
+                        c.accept[i] = 0; c.fin[i] = 0;
+                    }
+                }
+                wave_lds_sync();
+                more = any_active() && !x.aborted;
+                ph = 0;
+            } else if (!dopri) {
                 for (int s = 0; s < nts; ++s)
                     if (lq == 0) { c.accept[s * 16 + li] = 0; c.fin[s * 16 + li] = 0; }
                 wave_lds_sync();

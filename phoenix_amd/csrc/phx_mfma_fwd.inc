@@ -112,7 +112,9 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
         __syncthreads();
         return c.misc[0];
     };
+    const bool stepped = cfg.method != PHX_DOPRI5 && cfg.step > 0.0;   // options["step_size"]: sub-steps, dt per trajectory
     auto dt_of = [&](int lb, int i) -> float {   // fixed-grid dt of interval i (solvers.py:85-87)
+        if (stepped) return c.dtf[lb];           // ... or of the trajectory's running grid step
         const int b = rowof(lb);
         const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
         const double sg = (double)c.sgn[lb];
@@ -477,7 +479,94 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
         __syncthreads();
     };
 
-    if (cfg.method != PHX_DOPRI5) {
+    if (stepped) {
+        // ------------------------------------------------------------------ fixed grid with a step size (solvers.py:59-103)
+        // One grid per trajectory, anchored at its t[0]; a step writes the outputs it reaches or passes (the state at a
+        // grid point, else the linear interpolant); a trajectory whose grid has ended is masked like `done` in the dopri5
+        // arm.  Intermediate states never leave the private tiles.
+        const int S = fixed_nstages(cfg.method);
+        const bool tf32 = cfg.t_is_f32 != 0;
+        for (int lb = tid; lb < Bt; lb += blockDim.x) {
+            c.dtf[lb] = 0.f;
+            if (c.done[lb]) continue;
+            const TimeRow tb = trowT(t, T, cfg, shared ? 0 : rowof(lb));
+            const double sg = (double)c.sgn[lb];
+            c.nsiv[lb] = step_grid_steps(sg * tb[0], sg * tb[T - 1], cfg.step, tf32);
+            // max_num_steps: a budget of grid steps per call (a tiny step would hold the device for hours otherwise)
+            if ((long long)c.nsiv[lb] > cfg.max_steps) { c.st[lb] = PHX_ERR_MAX_STEPS; c.done[lb] = 1; }
+        }
+        int active = count_active();
+        while (active > 0 && !x.aborted) {
+            for (int lb = tid; lb < Bt; lb += blockDim.x) {
+                if (c.done[lb]) continue;
+                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : rowof(lb));
+                const double sg = (double)c.sgn[lb];
+                const int k = c.nsteps[lb], n = c.nsiv[lb];
+                const double g0 = c.rk_t1[lb];
+                const double g1 = step_grid_at(sg * tb[0], sg * tb[T - 1], cfg.step, tf32, n, k + 1);
+                c.rk_t0[lb] = g0; c.rk_t1[lb] = g1;
+                c.dtf[lb] = tf32 ? ((float)g1 - (float)g0) : (float)(g1 - g0);
+                int oi = c.out_idx[lb];
+                c.out_lo[lb] = oi;
+                while (oi < T && sg * tb[oi] <= g1) ++oi;
+                c.out_hi[lb] = oi; c.out_idx[lb] = oi;
+                c.nsteps[lb] = k + 1; c.nfe[lb] += S;
+                c.fin[lb] = (k + 1 >= n) ? 1 : 0;
+            }
+            __syncthreads();
+            for (int st = 0; st < S; ++st) eval(3, st, 0, st, 0);
+            for (int s = 0; s < d.TPW; ++s) {
+                const int ttl = wv * d.TPW + s;
+                if (ttl >= ntg) continue;   // helper wave: no trajectory tile of its own, it only serves the exchange
+                const int lb = ttl * 16 + li;
+                const int b = rowof(lb);
+                const float dtl = c.dtf[lb];
+                const bool active1 = !c.done[lb];
+                if (!__any(active1)) continue;
+                const int lo = c.out_lo[lb], hi = c.out_hi[lb];
+                const double g0 = c.rk_t0[lb], g1 = c.rk_t1[lb];
+                const double sg = (double)c.sgn[lb];
+                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+                for (int bl = 0; bl < nbl; ++bl) {
+                    float yv[8], y1[8], k0[8], k1[8], k2[8], k3[8];
+                    load8(tptr(V_Y0, ttl, bl), yv);
+                    load8(tptr(V_K0, ttl, bl), k0);
+                    if (S >= 2) load8(tptr(V_K0 + 1, ttl, bl), k1);
+                    if (S >= 4) { load8(tptr(V_K0 + 2, ttl, bl), k2); load8(tptr(V_K0 + 3, ttl, bl), k3); }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        if (cfg.method == PHX_EULER) y1[j] = yv[j] + dtl * k0[j];
+                        else if (cfg.method == PHX_MIDPOINT) y1[j] = yv[j] + dtl * k1[j];
+                        else y1[j] = yv[j] + (((k0[j] + 3.0f * (k1[j] + k2[j])) + k3[j]) * dtl) * 0.125f;
+                    }
+                    if (active1) {
+                        for (int jo = lo; jo < hi; ++jo) {   // _linear_interp (solvers.py:97-103)
+                            const double tj = sg * tb[jo];
+                            float ov[8];
+                            if (tj == g0) {
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) ov[j] = yv[j];
+                            } else if (tj == g1) {
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) ov[j] = y1[j];
+                            } else {
+                                const float slope = tf32 ? ((float)tj - (float)g0) / ((float)g1 - (float)g0)
+                                                         : (float)((tj - g0) / (g1 - g0));
+#pragma unroll
+                                for (int j = 0; j < 8; ++j) ov[j] = yv[j] + slope * (y1[j] - yv[j]);
+                            }
+                            row_store8(sol, (long long)jo * d.BN + (long long)b * N, (blk0 + bl) * 32 + gmap(lq, 0), N, b < B,
+                                       ov);
+                        }
+                        store8(tptr(V_Y0, ttl, bl), y1);   // per-lane select: a finished trajectory keeps its state
+                    }
+                }
+            }
+            __syncthreads();
+            if (tid < Bt && !c.done[tid] && c.fin[tid]) c.done[tid] = 1;
+            active = count_active();
+        }
+    } else if (cfg.method != PHX_DOPRI5) {
         // ------------------------------------------------------------------ fixed grid (solvers.py:77-95)
         const int S = fixed_nstages(cfg.method);
         for (int i = 0; i + 1 < T; ++i) {

@@ -21,6 +21,7 @@ struct SolveCfg {
                                                    // (float data, read as double on the fly: no conversion kernel)
     float rtol, atol;  // the reference multiplies fp32 tensors by these (cast to fp32)
     long long max_steps;
+    double step;       // options["step_size"] of a fixed-grid method (solvers.py:59-71); 0: one step per interval of t
 };
 
 // launch geometry (D1) and workspace pointers (W1) of the v1 / v2 / v3 MFMA kernels (phx_mfma_common.inc)
@@ -97,6 +98,28 @@ __device__ __forceinline__ float fixed_weight(int method, int st, float dt)
     if (method == PHX_EULER) return dt;
     if (method == PHX_MIDPOINT) return st == 1 ? dt : 0.f;
     return ((st == 0 || st == 3) ? 1.0f : 3.0f) * dt * 0.125f;
+}
+
+// The step grid of options["step_size"] (_grid_constructor_from_step_size, solvers.py:59-71) between `start` and `end`
+// (start < end, solver time): niters = ceil((end - start) / h + 1) points g_k = k * h + start, formed like the reference's
+// tensor expression -- unfused multiply and add in the dtype of the caller's t -- and the last one set to `end`.
+// step_grid_steps: niters - 1, at least 1.  step_grid_at: g_k; no point lies beyond `end` and g_n IS `end`, so a
+// quotient within rounding of an integer costs at most one step of (near) zero length, never a missing output.
+__device__ __forceinline__ int step_grid_steps(double start, double end, double h, bool f32)
+{
+    double q;
+    if (f32) q = (double)__fadd_rn(__fdiv_rn(__fsub_rn((float)end, (float)start), (float)h), 1.0f);
+    else q = __dadd_rn(__ddiv_rn(__dsub_rn(end, start), h), 1.0);
+    q = ceil(q);
+    if (!(q >= 2.0)) return 1;
+    return q > 2147483000.0 ? 2147483000 : (int)q - 1;
+}
+__device__ __forceinline__ double step_grid_at(double start, double end, double h, bool f32, int n, int k)
+{
+    if (k >= n) return end;
+    const double g = f32 ? (double)__fadd_rn(__fmul_rn((float)k, (float)h), (float)start)
+                         : __dadd_rn(__dmul_rn((double)k, h), start);
+    return g < end ? g : end;
 }
 
 // quartic dense output (interp.py:1-47) at fraction x of the step

@@ -400,13 +400,39 @@ def _solve_call(op, pkey, device, call):
     _ws_last[wkey] = pkey
 
 
+STEPPED_MAX_STEPS = 1000000   # default budget of grid steps (per call forward, per interval backward) under a step size
+
+
+def require_stepped_kernels(p, B, T, method, forward=True, backward=True):
+    """raises unless kernels with the sub-step loop plan this shape, in the directions asked for: before any launch, so
+    that a training step is not refused between its forward and its backward solve"""
+    lib, m = _lib.load(), _lib.METHODS[method] | 0x100
+    if forward and lib.phx_debug_forward_kernel_m(p.N, p.H, B, T, _lib.CTRL_PER_TRAJECTORY, m) == 0:
+        raise RuntimeError("phoenix_amd: bad argument: no forward kernel with the sub-step loop of options['step_size'] "
+                           "serves N=%d, H=%d under the current plan switches" % (p.N, p.H))
+    if backward and lib.phx_debug_adjoint_kernel_m(p.N, p.H, B, T, _lib.CTRL_PER_TRAJECTORY, m) == 0:
+        raise RuntimeError("phoenix_amd: bad argument: no backward kernel with the sub-step loop of options['step_size'] "
+                           "serves N=%d, H=%d under the current plan switches" % (p.N, p.H))
+
+
+def _step_of(method, step_size):
+    """the step size the stepped entry points get: 0.0 (= the plain entry point's behaviour) unless a fixed-grid method"""
+    return float(step_size) if step_size and method != "dopri5" else 0.0
+
+
 def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f32, max_num_steps=0, stats=None,
-                  calls=1):
+                  calls=1, step_size=0.0):
     """y0 [B,N] f32, t64 [T] or [B,T] f64 (device) -> sol [T,B,N], status[B], nfe[B], nsteps[B].
     The engine writes NaN into the outputs a failed trajectory never reached (a backward solve launched before the
     status is read then stops at once).  calls > 1 (shared control): the rows are `calls` independent odeint calls
-    of B/calls rows each, every call with its own step controller (include/phoenix_hip.h, phx_solve_opts.calls)."""
+    of B/calls rows each, every call with its own step controller (include/phoenix_hip.h, phx_solve_opts.calls).
+    step_size > 0 (fixed-grid methods): options["step_size"], phx_odeint_stepped."""
     B, N = y0.shape
+    step = _step_of(method, step_size)
+    if step and calls > 1:
+        raise ValueError("calls > 1 has no sub-step loop")
+    if step and not max_num_steps:
+        max_num_steps = STEPPED_MAX_STEPS
     if calls > 1 and (control != _lib.CTRL_SHARED or B % calls):
         raise ValueError("calls > 1 needs shared step control and B divisible by calls")
     T = t64.shape[-1]
@@ -415,10 +441,13 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
         stats = torch.empty((3, B), dtype=torch.int32, device=y0.device)
     p.on_current_stream()
     ws, nb = _workspace(_lib.OP_ODEINT, p.N, p.H, B, T, y0.device, calls)
-    pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), calls) + _plan_env()
+    pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), calls, step) + _plan_env()
 
     def call(keep):
         o = _opts(method, control, rtol, atol, t_per_sample, t_is_f32, max_num_steps, calls, keep)
+        if step:
+            return _lib.load().phx_odeint_stepped(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(sol), _p(stats[0]),
+                                                  _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr(), step)
         return _lib.load().phx_odeint(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(sol), _p(stats[0]),
                                       _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
 
@@ -427,22 +456,28 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
 
 
 def solve_adjoint(p, t64, y_saved, grad_y, method, control, rtol, atol, t_per_sample, t_is_f32, want_grads=True,
-                  max_num_steps=0, stats=None):
-    """y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps.  `stats`: an int32 [3,B] to use (rows contiguous)."""
+                  max_num_steps=0, stats=None, step_size=0.0):
+    """y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps.  `stats`: an int32 [3,B] to use (rows contiguous).
+    step_size > 0 (fixed-grid methods): the backward solve's own step, phx_odeint_adjoint_backward_stepped."""
     T, B, N = y_saved.shape
+    step = _step_of(method, step_size)
+    if step and not max_num_steps:
+        max_num_steps = STEPPED_MAX_STEPS
     adj = torch.empty((B, N), dtype=torch.float32, device=y_saved.device)
     if stats is None:
         stats = torch.empty((3, B), dtype=torch.int32, device=y_saved.device)
     grads = p.new_grads() if want_grads else None
     p.on_current_stream()
     ws, nb = _workspace(_lib.OP_ADJOINT, p.N, p.H, B, T, y_saved.device)
-    pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), bool(want_grads)) + _plan_env()
+    pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), bool(want_grads), step) + _plan_env()
 
     def call(keep):
         o = _opts(method, control, rtol, atol, t_per_sample, t_is_f32, max_num_steps, 1, keep)
-        return _lib.load().phx_odeint_adjoint_backward(
-            C.byref(p.c), _p(t64), B, T, C.byref(o), _p(y_saved), _p(grad_y), _p(adj),
-            C.byref(grads.c) if grads else None, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
+        args = (C.byref(p.c), _p(t64), B, T, C.byref(o), _p(y_saved), _p(grad_y), _p(adj),
+                C.byref(grads.c) if grads else None, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
+        if step:
+            return _lib.load().phx_odeint_adjoint_backward_stepped(*args, step)
+        return _lib.load().phx_odeint_adjoint_backward(*args)
 
     _solve_call(_lib.OP_ADJOINT, pkey, y_saved.device, call)
     return adj, grads, stats[0], stats[1], stats[2]

@@ -2,7 +2,8 @@
 
 PHOENIX's drivers only ever pass ODENet, which the fused HIP engine integrates; any other `func(t, y)` gets this plain
 PyTorch formulation on the caller's device: the same algorithms (fixed grid euler / midpoint / 3/8-rule rk4, one step per
-interval, solvers.py:77-95, fixed_grid.py, rk_common.py:96-103; dopri5 with the reference's initial step, FSAL, error
+interval or the grid of options["step_size"] with linear interpolation, solvers.py:59-103, fixed_grid.py,
+rk_common.py:96-103; dopri5 with the reference's initial step, FSAL, error
 ratio, step-size rule and quartic dense output, rk_common.py:39-228, misc.py:47-103, interp.py), one batch-wide step
 controller like the reference's `odeint`, every operation a torch op (so `odeint` is differentiable by plain
 backpropagation, as the reference's is, and `odeint_adjoint` integrates the augmented system of adjoint.py:32-162 with
@@ -56,14 +57,55 @@ def _interp(y0, y1, ym, f0, f1, dt, x):                                        #
     return y0 + x * (dt * f0 + x * (c + x * (b + x * a)))
 
 
-def integrate(func, y0, t, rtol, atol, method, norm=_rms, max_num_steps=2 ** 31 - 1):
-    """[len(t), *y0.shape]; `t` strictly monotone (either direction), time arithmetic in t's dtype promoted to fp64."""
+def _step_grid(t, h):
+    """the grid of options["step_size"] (solvers.py:59-71) for increasing host times `t`, in t's dtype: k * h + t[0] for
+    k < ceil((t[-1] - t[0]) / h + 1); no point beyond t[-1], and the last one IS t[-1] (a quotient within rounding of
+    an integer then costs a step of near-zero length where the reference's assert would fail)"""
+    niters = max(int(torch.ceil((t[-1] - t[0]) / h + 1).item()), 2)
+    g = torch.minimum(torch.arange(0, niters, dtype=t.dtype) * h + t[0], t[-1])
+    g[-1] = t[-1]
+    return g
+
+
+_STEPPED_MAX_STEPS = 1000000   # the engine's default budget of grid steps under a step size (engine.STEPPED_MAX_STEPS)
+
+
+def _integrate_stepped(func, y0, t, method, h, max_num_steps):
+    """fixed grid with a step size (solvers.py:77-103): `t` increasing, in the caller's dtype; grid logic on the host"""
+    th = t.detach().cpu()
+    budget = min(max_num_steps, _STEPPED_MAX_STEPS) if max_num_steps >= 2 ** 31 - 1 else max_num_steps
+    n = float(torch.ceil((th[-1] - th[0]) / h + 1)) - 1
+    assert n <= budget, "max_num_steps exceeded ({}>={})".format(int(n), budget)
+    g = _step_grid(th, h)
+    dts = (g[1:] - g[:-1]).to(device=y0.device, dtype=torch.float64)
+    g64 = g.to(device=y0.device, dtype=torch.float64)
+    out, y, j = [y0], y0, 1
+    for k in range(len(g) - 1):
+        y1 = _fixed_step(func, method, g64[k], dts[k], y)
+        while j < len(th) and bool(g[k + 1] >= th[j]):                          # _linear_interp, solvers.py:97-103
+            if bool(th[j] == g[k]):
+                out.append(y)
+            elif bool(th[j] == g[k + 1]):
+                out.append(y1)
+            else:
+                out.append(y + float((th[j] - g[k]) / (g[k + 1] - g[k])) * (y1 - y))
+            j += 1
+        y = y1
+    return torch.stack(out), len(g) - 1
+
+
+def integrate(func, y0, t, rtol, atol, method, norm=_rms, max_num_steps=2 ** 31 - 1, step_size=None):
+    """[len(t), *y0.shape]; `t` strictly monotone (either direction), time arithmetic in t's dtype promoted to fp64.
+    `step_size` (fixed-grid methods): the step grid is formed in t's own dtype, as the reference forms it."""
+    t_in = t
     t = t.to(torch.float64)
     if t.numel() > 1 and bool(t[0] > t[1]):                                    # misc.py:210-221: integrate y(-t) forwards
         f = func
         func = lambda tt, y: -f(-tt, y)                                        # noqa: E731
-        t = -t
+        t, t_in = -t, -t_in
     assert bool((t[1:] > t[:-1]).all()), "t must be strictly increasing or decreasing"
+    if method != "dopri5" and step_size and t.numel() > 1:
+        return _integrate_stepped(func, y0, t_in, method, step_size, max_num_steps)[0]
     out = [y0]
     if method != "dopri5":
         y = y0
@@ -131,9 +173,10 @@ class _AdjointFn(torch.autograd.Function):
     augmented system [vjp_t, y, adj_y, adj_params] integrated interval by interval in reverse time."""
 
     @staticmethod
-    def forward(ctx, func, y0, t, rtol, atol, method, adj, max_steps, *params):
+    def forward(ctx, func, y0, t, rtol, atol, method, adj, max_steps, steps, *params):
         with torch.no_grad():
-            sol = integrate(func, y0, t, rtol, atol, method, max_num_steps=max_steps)
+            sol = integrate(func, y0, t, rtol, atol, method, max_num_steps=max_steps, step_size=steps[0])
+        ctx.adj_step = steps[1]
         ctx.func, ctx.cfg, ctx.max_steps = func, adj, max_steps
         ctx.save_for_backward(t, sol, *params)
         return sol
@@ -161,7 +204,7 @@ class _AdjointFn(torch.autograd.Function):
             state = torch.cat([sol.new_zeros(1), sol[-1].reshape(-1), grad_sol[-1].reshape(-1), sol.new_zeros(npar)])
             for i in range(len(t) - 1, 0, -1):
                 state = integrate(aug, state, t[i - 1:i + 1].flip(0), rtol, atol, method, norm=norm,
-                                  max_num_steps=ctx.max_steps)[1].clone()
+                                  max_num_steps=ctx.max_steps, step_size=ctx.adj_step)[1].clone()
                 state[1:1 + ny] = sol[i - 1].reshape(-1)
                 state[1 + ny:1 + 2 * ny] += grad_sol[i - 1].reshape(-1)
         gy = state[1 + ny:1 + 2 * ny].view(shape)
@@ -169,17 +212,21 @@ class _AdjointFn(torch.autograd.Function):
         for p in params:
             gp.append(state[off:off + p.numel()].view_as(p))
             off += p.numel()
-        return (None, gy, None, None, None, None, None, None) + tuple(gp)
+        return (None, gy, None, None, None, None, None, None, None) + tuple(gp)
 
 
 def odeint(func, y0, t, rtol, atol, method, options):
     return integrate(func, y0, t.to(y0.device), rtol, atol, method,
-                     max_num_steps=int(options.get("max_num_steps", 2 ** 31 - 1)) or 2 ** 31 - 1)
+                     max_num_steps=int(options.get("max_num_steps", 2 ** 31 - 1)) or 2 ** 31 - 1,
+                     step_size=options.get("step_size"))
 
 
-def odeint_adjoint(func, y0, t, rtol, atol, method, options, adjoint_rtol, adjoint_atol, adjoint_method, adjoint_params):
+def odeint_adjoint(func, y0, t, rtol, atol, method, options, adjoint_rtol, adjoint_atol, adjoint_method, adjoint_params,
+                   adjoint_step_size=None):
+    """adjoint_step_size: step of the backward solve's per-interval grids (adjoint_options["step_size"], resolved by the
+    caller: it defaults to the forward's, adjoint.py:182-183)"""
     if adjoint_params is None:                                                 # find_parameters, adjoint.py:207-218
         adjoint_params = tuple(p for p in func.parameters() if p.requires_grad) if isinstance(func, torch.nn.Module) else ()
     max_steps = int(options.get("max_num_steps", 2 ** 31 - 1)) or 2 ** 31 - 1
     return _AdjointFn.apply(func, y0, t.to(y0.device), rtol, atol, method, (adjoint_rtol, adjoint_atol, adjoint_method),
-                            max_steps, *adjoint_params)
+                            max_steps, (options.get("step_size"), adjoint_step_size), *adjoint_params)

@@ -10,6 +10,7 @@ exceptions (ValueError for an unknown method, AssertionError for the solver asse
 Extension (what the reference's training loop *means*, train_insilico.py:128-130): `t` may be 2-D
 `[B, T]` -- one time grid per sample of `y0 [B, 1, N]` -- which integrates all B samples in ONE launch
 with an independent step controller per sample (`odeint_per_sample` is the explicit spelling)."""
+import math
 import warnings
 
 import torch
@@ -21,12 +22,29 @@ from .odenet import params_of
 SOLVERS = ("dopri8", "dopri5", "bosh3", "adaptive_heun", "euler", "midpoint", "rk4", "explicit_adams",
            "implicit_adams", "fixed_adams")
 _ENGINE_METHODS = ("dopri5", "euler", "midpoint", "rk4")
-_KNOWN_UNSUPPORTED_OPTIONS = ("step_size", "grid_constructor", "grid_points", "eps", "first_step", "safety",
+_FIXED_GRID_METHODS = ("euler", "midpoint", "rk4")
+_KNOWN_UNSUPPORTED_OPTIONS = ("grid_constructor", "grid_points", "eps", "first_step", "safety",
                               "ifactor", "dfactor", "norm", "dtype")
 
 
+def _step_size(value):
+    """options["step_size"] as a float: a Python number or a 0-d tensor, positive and finite"""
+    if torch.is_tensor(value):
+        if value.numel() != 1:
+            raise ValueError("phoenix_amd: step_size must be a number or a 0-d tensor")
+        value = value.item()
+    try:
+        h = float(value)
+    except (TypeError, ValueError):
+        raise ValueError("phoenix_amd: step_size must be a positive finite number, got %r" % (value,)) from None
+    if not (h > 0.0 and math.isfinite(h)):
+        raise ValueError("phoenix_amd: step_size must be a positive finite number, got %r" % (value,))
+    return h
+
+
 def _check_inputs(func, y0, t, rtol, atol, method, options):
-    """misc.py:165-241, restricted to what the engine supports."""
+    """misc.py:165-241, restricted to what the engine supports.  options["step_size"] comes back validated, as a float,
+    for the fixed-grid methods; dopri5 drops it with the reference's warning (misc.py:204-206)."""
     if not torch.is_tensor(y0):
         raise NotImplementedError("phoenix_amd: tuple states are not supported (PHOENIX passes a single tensor)")
     if not torch.is_floating_point(y0):
@@ -50,7 +68,9 @@ def _check_inputs(func, y0, t, rtol, atol, method, options):
     for k in list(options):
         if k in _KNOWN_UNSUPPORTED_OPTIONS:
             raise NotImplementedError("phoenix_amd: solver option '%s' is not supported by the fused stepper" % k)
-        if k not in ("max_num_steps", "batch_control"):
+        if k == "step_size" and method in _FIXED_GRID_METHODS:
+            options[k] = _step_size(options[k])
+        elif k not in ("max_num_steps", "batch_control"):
             warnings.warn("phoenix_amd: Unexpected arguments {}".format({k: options.pop(k)}))
     if torch.is_tensor(rtol) or torch.is_tensor(atol):
         rtol, atol = float(rtol), float(atol)
@@ -104,16 +124,23 @@ class _OdeintAdjointFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y2, t64, cfg, ws, bs, wp, bp, wa, g):
-        (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, defer) = cfg
+        (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, defer, steps) = cfg
         engine.check_pending_status()
         p = engine.params_cached(ws, bs, wp, bp, wa, g)
+        if steps[0] or steps[1]:      # both solves of the step, or neither
+            B, T = y2.shape[0], t64.shape[-1]
+            if steps[0]:
+                engine.require_stepped_kernels(p, B, T, method, backward=False)
+            if steps[1] and defer:    # (defer: a backward pass can come)
+                engine.require_stepped_kernels(p, B, T, adj[0], forward=False)
         # one stats block for both launches of the step, [status | nfe | nsteps][launch: forward, backward][B]: the two
         # status rows are contiguous (one copy to the host), and nothing is zero-filled -- every solve kernel writes the
         # three entries of every trajectory of its launch
         stats = torch.empty((3, 2 if defer else 1, y2.shape[0]), dtype=torch.int32, device=y2.device)
         ctx.set_materialize_grads(False)      # no zero tensor for the (non-differentiable) nfe output in backward
         sol, status, nfe, nsteps = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol,
-                                                        atol, per_sample, t_is_f32, max_steps, stats=stats[:, 0])
+                                                        atol, per_sample, t_is_f32, max_steps, stats=stats[:, 0],
+                                                        step_size=steps[0])
         # The reference raises the solver's AssertionErrors synchronously.  When a backward pass is coming
         # (some input requires grad) the forward status is read together with the backward solve's status, in
         # ONE host<->device round trip per training step after both launches are queued: same exception (the
@@ -135,7 +162,7 @@ class _OdeintAdjointFn(torch.autograd.Function):
         t64, sol, ws, bs, wp, bp, wa, g = ctx.saved_tensors
         if grad_sol is None:
             grad_sol = torch.zeros_like(sol)
-        (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, _defer) = ctx.cfg
+        (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, _defer, steps) = ctx.cfg
         a_method, a_rtol, a_atol, via_odeint = adj
         if via_odeint and a_method != "dopri5":
             raise NotImplementedError(
@@ -149,7 +176,8 @@ class _OdeintAdjointFn(torch.autograd.Function):
         need_p = any(ctx.needs_input_grad[3:])
         adj_y0, grads, status, _nfe, _ns = engine.solve_adjoint(
             p, t64, sol, grad_sol.contiguous(), a_method, control, a_rtol, a_atol, per_sample, t_is_f32,
-            want_grads=need_p, max_num_steps=max_steps, stats=None if ctx.phx_stats is None else ctx.phx_stats[:, 1])
+            want_grads=need_p, max_num_steps=max_steps, stats=None if ctx.phx_stats is None else ctx.phx_stats[:, 1],
+            step_size=steps[1])
         # The status read-back is the one host<->device round trip of a training step.  It is queued as an
         # end-of-backward callback of the autograd engine (the mechanism DDP finalises with): the exception still comes
         # out of loss.backward(), but the host returns the gradients and runs its accumulation nodes while the kernel
@@ -175,8 +203,9 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
       * nothing requires grad, autograd is off (validation, analysis callers), or `return_stats`: plain forward solve;
       * something requires grad: the call is routed through `odeint_adjoint`, so the result IS differentiable.  With
         dopri5 the continuous adjoint agrees with backpropagation through the converged solve to the solver tolerance
-        (<= 2e-6 relative).  With a fixed grid (euler / midpoint / rk4: ONE step per interval,
-        far from converged) the two differ at O(1), and returning the adjoint's gradient silently would not be the
+        (<= 2e-6 relative).  With a fixed grid (euler / midpoint / rk4: one step per interval, or
+        the steps of options["step_size"]; not converged in general) the two differ, at O(1) for one step per interval,
+        and returning the adjoint's gradient silently would not be the
         reference's `odeint`: the BACKWARD pass of such a call raises NotImplementedError (the forward result is
         exact either way; PHOENIX itself trains through `odeint_adjoint`, train_insilico.py:15-18, which is
         reproduced operation for operation)."""
@@ -191,7 +220,8 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
     engine.check_pending_status()
     p = engine.params_cached(*params)
     sol, status, nfe, nsteps = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol,
-                                                    per_sample, t_is_f32, int(options.get("max_num_steps", 0)))
+                                                    per_sample, t_is_f32, int(options.get("max_num_steps", 0)),
+                                                    step_size=options.get("step_size", 0.0))
     engine.raise_for_status(status)
     out = _out_shape(sol, y0, per_sample)
     return (out, nfe, nsteps) if return_stats else out
@@ -212,6 +242,9 @@ def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t, options)
     if per_sample or control != _lib.CTRL_SHARED:
         raise ValueError("odeint_calls: one shared time grid, batch_control='shared'")
+    if options.get("step_size"):      # the batched launch has no sub-step loop: the K calls themselves
+        with torch.no_grad():
+            return torch.stack([odeint(func, y0s[k], t, rtol, atol, method, options) for k in range(K)])
     engine.check_pending_status()
     p = engine.params_cached(*params)
     try:
@@ -224,23 +257,36 @@ def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     return sol.reshape((sol.shape[0], K) + tuple(y0s.shape[1:])).transpose(0, 1)
 
 
+def _adjoint_step(options, a_step, adjoint_method):
+    """step size of the backward solve: adjoint_options["step_size"], else the forward's; none for dopri5"""
+    if adjoint_method not in _FIXED_GRID_METHODS:
+        return 0.0
+    return options.get("step_size", 0.0) if a_step is None else a_step
+
+
 def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint_rtol=None,
                    adjoint_atol=None, adjoint_method=None, adjoint_options=None, adjoint_params=None, _via_odeint=False):
     """adjoint.py:165-204.  Gradients flow to y0 and to the six ODENet parameters."""
+    # adjoint_options may hold step_size and nothing else; absent, the backward solve inherits the forward's step
+    # (adjoint.py:182-183: adjoint_options defaults to options)
+    adjoint_options = {} if adjoint_options is None else dict(adjoint_options)
+    a_step = adjoint_options.pop("step_size", None)
+    if adjoint_options:
+        raise NotImplementedError("phoenix_amd: adjoint_options other than step_size are not supported (got %s)"
+                                  % sorted(adjoint_options))
+    if a_step is not None:
+        a_step = _step_size(a_step)
     if not _is_odenet(func):      # any other module: the reference's augmented system on the unfused torch stepper
-        if adjoint_options:
-            raise NotImplementedError("phoenix_amd: adjoint_options are not supported")
         y0, t, rtol, atol, method, options = _check_inputs(func, y0, t, rtol, atol, method, options)
         engine._require_gpu(y0, "y0")          # like every other entry point: no CPU compute path in this package
         assert t.ndimension() == 1, "per-sample time grids need a PHOENIX ODENet"
         return generic.odeint_adjoint(func, y0, t, rtol, atol, method, options,
                                       rtol if adjoint_rtol is None else adjoint_rtol,
                                       atol if adjoint_atol is None else adjoint_atol,
-                                      method if adjoint_method is None else adjoint_method, adjoint_params)
+                                      method if adjoint_method is None else adjoint_method, adjoint_params,
+                                      options.get("step_size") if a_step is None else a_step)
     if adjoint_params is not None:
         raise NotImplementedError("phoenix_amd: adjoint_params is fixed to ODENet's six parameters")
-    if adjoint_options:
-        raise NotImplementedError("phoenix_amd: adjoint_options are not supported by the fused stepper")
     if adjoint_rtol is None:
         adjoint_rtol = rtol
     if adjoint_atol is None:
@@ -250,6 +296,8 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
         adjoint_method = method
     if adjoint_method not in _ENGINE_METHODS:
         raise NotImplementedError("phoenix_amd: adjoint_method '%s' not supported" % adjoint_method)
+    if a_step is not None and adjoint_method not in _FIXED_GRID_METHODS:      # as options with dopri5 (misc.py:204-206)
+        warnings.warn("phoenix_amd: Unexpected arguments {}".format({"step_size": a_step}))
     params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t, options)
     # The forward status is read together with the backward solve's only when a backward pass can come: autograd must
     # be recording AND something must require grad (needs_input_grad mirrors .requires_grad even under no_grad: the
@@ -257,7 +305,8 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     # (a plain `odeint` call routed here keeps the reference's synchronous asserts: its caller may never run backward)
     defer = torch.is_grad_enabled() and (y0.requires_grad or any(x.requires_grad for x in params)) and not _via_odeint
     cfg = (method, control, rtol, atol, per_sample, t_is_f32, int(options.get("max_num_steps", 0)),
-           (adjoint_method, float(adjoint_rtol), float(adjoint_atol), bool(_via_odeint)), defer)
+           (adjoint_method, float(adjoint_rtol), float(adjoint_atol), bool(_via_odeint)), defer,
+           (options.get("step_size", 0.0), _adjoint_step(options, a_step, adjoint_method)))
     sol, _nfe = _OdeintAdjointFn.apply(y2, t64, cfg, *params)
     return _out_shape(sol, y0, per_sample)
 
