@@ -172,6 +172,41 @@ int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t, in
                                         int *status, int *nfe, int *nsteps, void *workspace,
                                         size_t workspace_bytes, void *stream, double step_size);
 
+/* Backward pass of `odeint` itself with a fixed-grid method (torchdiffeq/_impl/odeint.py:30-74 returns an autograd-tracked
+ * solution): backpropagation through the solver's own euler / midpoint / rk4 steps (fixed_grid.py:6-38, rk_common.py:96-103),
+ * i.e. the DISCRETE adjoint -- the exact gradient of the numbers phx_odeint / phx_odeint_stepped produced, whatever the
+ * step.  NOT the continuous adjoint of phx_odeint_adjoint_backward, from which it differs at O(1) for one unconverged step
+ * per interval.  Arguments as phx_odeint_adjoint_backward_stepped: y_saved [T,B,N] forward outputs, grad_y [T,B,N], adj_y0
+ * [B,N] (overwritten), grads (+= or =, summed over B), status / nfe / nsteps [B], caller-owned workspace.
+ *   step_size <= 0: the grid is t itself; the start state of step i is y_saved[i]; grid_steps is ignored.
+ *   step_size > 0:  the grid of phx_odeint_stepped (one per trajectory, anchored at t[0], last step clipped, outputs between
+ *     grid points linearly interpolated: an output at fraction th of step k hands (1 - th) grad_y to grid state k and
+ *     th grad_y to grid state k + 1).  The kernel re-runs the forward grid from y_saved[0], keeps the start state of every
+ *     step in the checkpoint region of the workspace ([grid_steps][rows of a launch][N] floats) and sweeps back over them.
+ *     grid_steps >= the largest number of grid steps of any trajectory (PHX_ERR_WORKSPACE in status for one with more).
+ *   opts->max_num_steps > 0: the forward call's budget of grid steps per trajectory (PHX_ERR_MAX_STEPS in status).
+ *   nsteps [B] = grid steps swept back; nfe [B] = RHS evaluations and RHS vector-Jacobian products together: per grid
+ *   step s - 1 evaluations that rebuild the stage inputs and s products (2 s - 1), plus the s of the forward re-run under a
+ *   step size (3 s - 1), s = stages of the method.
+ * One persistent launch (k1_solve_bp) per chunk of the batch plus the gradient reduction.  Served: H <= 128.
+ * PHX_ERR_BAD_ARG before any device call: null pointers, non-positive sizes, method dopri5 (no backpropagation through
+ * adaptive steps), step_size > 0 with grid_steps < 1; PHX_ERR_BAD_ARG also for a shape no kernel plans (H > 128,
+ * PHX_ENGINE=v0); PHX_ERR_WORKSPACE when workspace_bytes < phx_odeint_backprop_workspace_bytes(N, H, B, T, grid_steps).
+ *
+ * phx_odeint_backprop_workspace_bytes(N, H, B, T, K) = phx_odeint_backprop_workspace_bytes(N, H, B, T, 0)
+ *     + 256 * ceil(K * Bc * N * 4 / 256),   Bc = rows of the call's largest launch (B when
+ * phx_debug_backprop_launches(N, H, B, T, method) == 1, else the chunk the shared driver walks the batch in); 0: no kernel
+ * plans the shape.  Sized for 256 CUs when no device is visible.  K = 0 when the call has no step size.
+ * phx_debug_backprop_kernel_m: 5 = k1_solve_bp serves the shape, 0 = refused.  phx_debug_backprop_launches: launches of
+ * that kernel one call makes (0: refused). */
+size_t phx_odeint_backprop_workspace_bytes(int N, int H, int B, int T, long long grid_steps);
+int phx_odeint_backprop_backward(const phx_params *p, const double *t, int B, int T, const phx_solve_opts *opts,
+                                 const float *y_saved, const float *grad_y, float *adj_y0, const phx_grads *grads,
+                                 int *status, int *nfe, int *nsteps, void *workspace, size_t workspace_bytes,
+                                 void *stream, double step_size, long long grid_steps);
+int phx_debug_backprop_kernel_m(int N, int H, int B, int T, int method);
+int phx_debug_backprop_launches(int N, int H, int B, int T, int method);
+
 /* prior_grad = X[K,N] @ P[N,N] with the prior matrix P in CSC form
  * (colptr [N+1], rowidx/vals [nnz], rows ascending inside a column).  Replaces the reference's dense
  * `torch.matmul(batch_for_prior, prior_mat)` (train_insilico.py:207-211) and the 0.5 GB dense matrix that

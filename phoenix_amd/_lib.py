@@ -31,7 +31,8 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_calls_workspace_bytes", "phx_weight_image_bytes", "phx_pack_weight_images", "phx_prior_targets_sell",
            "phx_debug_adjoint_kernel_m", "phx_prior_z_bytes", "phx_prior_mse_save", "phx_prior_vjp_saved",
            "phx_layout_params", "phx_debug_forward_kernel_m", "phx_debug_queue_kernel_events", "phx_debug_solve_launches",
-           "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped")
+           "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped", "phx_odeint_backprop_backward",
+           "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -78,6 +79,11 @@ def load():
                                                 vp, vp, vp, C.POINTER(PhxGrads), vp, vp, vp, vp, C.c_size_t, vp]
     lib.phx_odeint_stepped.argtypes = lib.phx_odeint.argtypes + [C.c_double]
     lib.phx_odeint_adjoint_backward_stepped.argtypes = lib.phx_odeint_adjoint_backward.argtypes + [C.c_double]
+    lib.phx_odeint_backprop_backward.argtypes = lib.phx_odeint_adjoint_backward.argtypes + [C.c_double, C.c_longlong]
+    lib.phx_odeint_backprop_workspace_bytes.argtypes = [C.c_int] * 4 + [C.c_longlong]
+    lib.phx_odeint_backprop_workspace_bytes.restype = C.c_size_t
+    lib.phx_debug_backprop_kernel_m.argtypes = [C.c_int] * 5
+    lib.phx_debug_backprop_launches.argtypes = [C.c_int] * 5
     lib.phx_prior_targets.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.phx_prior_targets_sell.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.phx_prior_mse.argtypes = [C.POINTER(PhxParams), vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]

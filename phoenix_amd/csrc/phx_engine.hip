@@ -1046,6 +1046,7 @@ struct SolveCall {
     hipStream_t st;
     double step = 0.0;   // SolveCfg::step
     int control = -1;    // >= 0: the step control the launches are planned and run with instead of o->control
+    float *ckpt = nullptr;   // k1_solve_bp: the checkpoint region behind the launches' layouts
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1108,6 +1109,7 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
         w.wimg = (const float *)(base + L.wimg);
         w.hq = (float *)(base + L.hq);
         a.PP = L.pp;
+        a.ckpt = c.ckpt;
         // header + exchange buffers are contiguous: one fill -- unless the caller vouches for the workspace (ws_keep: the
         // previous call on it was this one, same shape, same options), the batch is one launch and the kernel cleans
         // its idle exchange set itself (the kernels then alternate between the two sets)
@@ -1620,6 +1622,28 @@ int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, in
     return (B + k.chunk - 1) / k.chunk;
 }
 
+int phx_debug_backprop_kernel_m(int N, int H, int B, int T, int method)
+{
+    if (N <= 0 || H <= 0 || B <= 0 || T < 1 || method < PHX_EULER || method > PHX_RK4) return 0;
+    return bp_chunk(num_cus(), N, H, B, T) > 0 ? bp_backend().id : 0;
+}
+
+int phx_debug_backprop_launches(int N, int H, int B, int T, int method)
+{
+    if (phx_debug_backprop_kernel_m(N, H, B, T, method) == 0) return 0;
+    const int chunk = bp_chunk(num_cus(), N, H, B, T);
+    return (B + chunk - 1) / chunk;
+}
+
+size_t phx_odeint_backprop_workspace_bytes(int N, int H, int B, int T, long long grid_steps)
+{
+    if (N <= 0 || H <= 0 || B <= 0 || T < 1 || grid_steps < 0) return 0;
+    const int cus = num_cus();
+    const int chunk = bp_chunk(cus, N, H, B, T);
+    if (chunk <= 0) return 0;
+    return bp_base_bytes(cus, N, H, B, T) + align_up((size_t)grid_steps * chunk * N * 4, 256);
+}
+
 size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 0) return 0;
@@ -1931,6 +1955,40 @@ int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t_all
     if (hipGetLastError() != hipSuccess) return PHX_ERR_LAUNCH;
     if (grads) return launch_reduce(d, w, grads, st);
     return PHX_OK;
+}
+
+int phx_odeint_backprop_backward(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o,
+                                 const float *y_saved_all, const float *grad_y_all, float *adj_y0_all,
+                                 const phx_grads *grads, int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
+                                 size_t workspace_bytes, void *stream, double step_size, long long grid_steps)
+{
+    if (bad_params(p) || !t_all || !o || !y_saved_all || !grad_y_all || !adj_y0_all || !status_all || !nfe_all ||
+        !nsteps_all || B <= 0 || T < 1 || !workspace || grid_steps < 0 || grid_steps > 2147483000LL)
+        return PHX_ERR_BAD_ARG;
+    if (grads && (!grads->Ws || !grads->bs || !grads->Wp || !grads->bp || (!grads->WaT && !grads->Wa) || !grads->g))
+        return PHX_ERR_BAD_ARG;
+    if (o->method < PHX_EULER || o->method > PHX_RK4) return PHX_ERR_BAD_ARG;   // dopri5: no backpropagation through its steps
+    if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
+    const bool stepped = is_stepped(o, step_size);
+    if (stepped && grid_steps < 1) return PHX_ERR_BAD_ARG;
+    const int cus = num_cus();
+    if (cus <= 0) return PHX_ERR_LAUNCH;
+    const int chunk = bp_chunk(cus, p->N, p->H, B, T);
+    if (chunk <= 0) return PHX_ERR_BAD_ARG;   // H > 128, or PHX_ENGINE=v0
+    const int K = stepped ? (int)grid_steps : 0;
+    const size_t base = bp_base_bytes(cus, p->N, p->H, B, T);
+    if (workspace_bytes < base + align_up((size_t)K * chunk * p->N * 4, 256)) return PHX_ERR_WORKSPACE;
+    SolveCall c{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all, nfe_all, nsteps_all,
+                grads, workspace, workspace_bytes, (hipStream_t)stream};
+    c.step = stepped ? step_size : 0.0;
+    c.control = PHX_CTRL_PER_TRAJECTORY;
+    c.ckpt = K ? reinterpret_cast<float *>(static_cast<char *>(workspace) + base) : nullptr;
+    const Backend &be = bp_backend();
+    return run_solve(be, chunk, [&](int bc, D1 *d) {
+        if (!be.plan(p->N, p->H, bc, T, c.control, o->method, d)) return false;
+        d->K = K;
+        return true;
+    }, c);
 }
 
 }  // extern "C"

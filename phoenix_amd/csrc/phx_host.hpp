@@ -173,6 +173,7 @@ struct SolveArgs {
     int *status, *nfe, *nsteps;
     int grads;            // backward: 1 = parameter gradients wanted
     long long PP;         // backward: Regions::pp
+    float *ckpt;          // k1_solve_bp: checkpoint region [D1::K][rows of the launch][N] (null: none)
 };
 
 struct Backend {
@@ -212,5 +213,11 @@ const Backend &fwd3c_backend();
 const Backend &adj2_backend();
 const Backend &adj3_backend();
 const Backend &adj3c_backend();
+// k1_solve_bp (backpropagation through the fixed-grid steps): not in the lists of the adjoint direction, it has entry
+// points of its own.  bp_chunk: rows per launch of a batch (0: no plan); bp_base_bytes: workspace in front of the
+// checkpoint region; both size for 256 CUs when cus <= 0 (no device in sight).
+const Backend &bp_backend();
+int bp_chunk(int cus, int N, int H, int B, int T);
+size_t bp_base_bytes(int cus, int N, int H, int B, int T);
 
 }  // namespace phxh

@@ -47,6 +47,7 @@ struct D1 {
                // workgroup's gene blocks stay LDS resident, 0 = one chunk slot, re-staged as the sweeps walk the chunks
     int hb;    // chunked kernels: 1 = HALF-BLOCK gene tiles (G = 2 * nblk workgroups per batch group, 16 genes each)
     int split; // chunked kernels: > 1 = the waves of a trajectory tile take its gene blocks (block `wave / ntg`), partial rows added in LDS
+    int K;     // k1_solve_bp: grid steps per trajectory the checkpoint region of the workspace holds (0: none)
 };
 
 struct W1 {

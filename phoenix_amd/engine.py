@@ -415,6 +415,46 @@ def require_stepped_kernels(p, B, T, method, forward=True, backward=True):
                            "serves N=%d, H=%d under the current plan switches" % (p.N, p.H))
 
 
+# Backpropagation through the steps of options["step_size"] (solve_backprop) keeps the start state of every grid step:
+# K * B * N * 4 bytes for K steps.  The cap is what one backward pass may ask for: 1 GiB, i.e. ~3000 steps of 256
+# trajectories at the in-silico scale (N = 350) and 90 steps of 256 trajectories at breast-cancer scale (N = 11165) -- far
+# above what a fixed grid is chosen for (a handful of steps per interval), well below the device's memory, so that a
+# mistyped step size is refused at the call instead of allocating tens of gigabytes.
+BACKPROP_MAX_CHECKPOINT_BYTES = 1 << 30
+
+
+def backprop_grid_steps(t64, step_size):
+    """largest number of grid steps any trajectory of t64 ([T] or [B, T], in the dtype the engine reads) takes under
+    `step_size` -- the count phx_odeint_stepped's grid has (solvers.py:59-71: ceil((t_end - t_0) / h + 1) points, formed
+    in the dtype of t); one read of the device when t lives there"""
+    if t64.shape[-1] < 2:
+        return 1
+    q = ((t64[..., -1] - t64[..., 0]).abs() / step_size + 1).ceil().max().item()
+    if not q == q or q > 2147483000.0:      # non-finite t: the kernel reports it
+        return 2147483000 if q == q else 1
+    return max(int(q) - 1, 1)
+
+
+def require_backprop(N, H, B, T, method, t64=None, step_size=0.0):
+    """raises unless the backward pass of `odeint(method=<fixed grid>)` can serve this call, before anything is launched:
+    the kernel must plan the shape (H <= 128, not PHX_ENGINE=v0) and the checkpoints of a step size must fit
+    BACKPROP_MAX_CHECKPOINT_BYTES.  Returns the number of grid steps to size the workspace for (0: no step size)."""
+    if _lib.load().phx_debug_backprop_kernel_m(N, H, B, T, _lib.METHODS[method]) == 0:
+        raise RuntimeError("phoenix_amd: bad argument: backpropagation through odeint(method='%s') serves hidden layers "
+                           "up to H = 128 on the MFMA engine; N=%d, H=%d under the current plan switches is not served "
+                           "(use odeint_adjoint, the continuous adjoint)" % (method, N, H))
+    step = _step_of(method, step_size)
+    if not step:
+        return 0
+    K = backprop_grid_steps(t64, step)
+    if K * B * N * 4 > BACKPROP_MAX_CHECKPOINT_BYTES:
+        raise RuntimeError("phoenix_amd: backpropagation through %d grid steps of step_size=%g needs %d bytes of "
+                           "checkpoints (steps x %d trajectories x %d genes x 4), over the cap "
+                           "engine.BACKPROP_MAX_CHECKPOINT_BYTES = %d; use a larger step, or odeint_adjoint"
+                           % (K, step, K * B * N * 4, B, N, BACKPROP_MAX_CHECKPOINT_BYTES))
+    return K
+
+
 def _step_of(method, step_size):
     """the step size the stepped entry points get: 0.0 (= the plain entry point's behaviour) unless a fixed-grid method"""
     return float(step_size) if step_size and method != "dopri5" else 0.0
@@ -480,4 +520,50 @@ def solve_adjoint(p, t64, y_saved, grad_y, method, control, rtol, atol, t_per_sa
         return _lib.load().phx_odeint_adjoint_backward(*args)
 
     _solve_call(_lib.OP_ADJOINT, pkey, y_saved.device, call)
+    return adj, grads, stats[0], stats[1], stats[2]
+
+
+OP_BACKPROP = 4      # workspace-cache key of solve_backprop (phx_odeint_backprop_workspace_bytes sizes it, not phx_op)
+
+
+def _workspace_backprop(N, H, B, T, K, device):
+    key = (OP_BACKPROP, N, H, B, T, K) + _plan_env()
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _lib.load().phx_odeint_backprop_workspace_bytes(N, H, B, T, K)
+        _ws_bytes[key] = nbytes
+    key = (device.index, _stream_raw(device.index), OP_BACKPROP)
+    buf = _ws_cache.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=device)
+        _ws_cache[key] = buf
+        _ws_last.pop(key, None)
+    return buf, nbytes
+
+
+def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_f32, want_grads=True, max_num_steps=0,
+                   stats=None, step_size=0.0, grid_steps=0):
+    """backpropagation through the fixed-grid steps of the forward solve (phx_odeint_backprop_backward):
+    y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps, like solve_adjoint.  `grid_steps`: what
+    require_backprop returned for this call (the checkpoints of a step size)."""
+    T, B, N = y_saved.shape
+    step = _step_of(method, step_size)
+    if step and not max_num_steps:
+        max_num_steps = STEPPED_MAX_STEPS
+    adj = torch.empty((B, N), dtype=torch.float32, device=y_saved.device)
+    if stats is None:
+        stats = torch.empty((3, B), dtype=torch.int32, device=y_saved.device)
+    grads = p.new_grads() if want_grads else None
+    p.on_current_stream()
+    K = int(grid_steps) if step else 0
+    ws, nb = _workspace_backprop(p.N, p.H, B, T, K, y_saved.device)
+    pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), bool(want_grads), step, K) + _plan_env()
+
+    def call(keep):
+        o = _opts(method, control, 0.0, 0.0, t_per_sample, t_is_f32, max_num_steps, 1, keep)
+        return _lib.load().phx_odeint_backprop_backward(
+            C.byref(p.c), _p(t64), B, T, C.byref(o), _p(y_saved), _p(grad_y), _p(adj), C.byref(grads.c) if grads else None,
+            _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr(), step, K)
+
+    _solve_call(OP_BACKPROP, pkey, y_saved.device, call)
     return adj, grads, stats[0], stats[1], stats[2]

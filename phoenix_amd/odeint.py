@@ -126,12 +126,18 @@ class _OdeintAdjointFn(torch.autograd.Function):
     def forward(ctx, y2, t64, cfg, ws, bs, wp, bp, wa, g):
         (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, defer, steps) = cfg
         engine.check_pending_status()
+        # odeint(method=<fixed grid>) whose backward pass backpropagates through the steps: every shape that pass would
+        # refuse is refused HERE, at the call, before anything is launched (H > 128, PHX_ENGINE=v0, a grid whose
+        # checkpoints exceed engine.BACKPROP_MAX_CHECKPOINT_BYTES)
+        backprop = adj[3] and adj[0] in _FIXED_GRID_METHODS
+        ctx.phx_bp_steps = (engine.require_backprop(ws.shape[1], ws.shape[0], y2.shape[0], t64.shape[-1], method, t64, steps[0])
+                            if backprop else 0)
         p = engine.params_cached(ws, bs, wp, bp, wa, g)
         if steps[0] or steps[1]:      # both solves of the step, or neither
             B, T = y2.shape[0], t64.shape[-1]
             if steps[0]:
                 engine.require_stepped_kernels(p, B, T, method, backward=False)
-            if steps[1] and defer:    # (defer: a backward pass can come)
+            if steps[1] and defer and not backprop:    # (defer: a backward pass can come)
                 engine.require_stepped_kernels(p, B, T, adj[0], forward=False)
         # one stats block for both launches of the step, [status | nfe | nsteps][launch: forward, backward][B]: the two
         # status rows are contiguous (one copy to the host), and nothing is zero-filled -- every solve kernel writes the
@@ -164,20 +170,21 @@ class _OdeintAdjointFn(torch.autograd.Function):
             grad_sol = torch.zeros_like(sol)
         (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, _defer, steps) = ctx.cfg
         a_method, a_rtol, a_atol, via_odeint = adj
-        if via_odeint and a_method != "dopri5":
-            raise NotImplementedError(
-                "phoenix_amd: backward through odeint(method='%s') on an ODENet would need backpropagation through the "
-                "fixed-grid steps, which the fused stepper does not record (the continuous adjoint differs from it at "
-                "O(1) for one unconverged step per interval); use odeint_adjoint -- the reference's training path, "
-                "adjoint.py:165" % a_method)
         p = ctx.phx_params
         if ctx.phx_versions != tuple(x._version for x in (ws, bs, wp, bp, wa, g)):
             p = engine.params_cached(ws, bs, wp, bp, wa, g)   # parameters were modified in place since forward
         need_p = any(ctx.needs_input_grad[3:])
-        adj_y0, grads, status, _nfe, _ns = engine.solve_adjoint(
-            p, t64, sol, grad_sol.contiguous(), a_method, control, a_rtol, a_atol, per_sample, t_is_f32,
-            want_grads=need_p, max_num_steps=max_steps, stats=None if ctx.phx_stats is None else ctx.phx_stats[:, 1],
-            step_size=steps[1])
+        bstats = None if ctx.phx_stats is None else ctx.phx_stats[:, 1]
+        if via_odeint and a_method in _FIXED_GRID_METHODS:
+            # the reference's `odeint`: backpropagation through the solver's own steps (the discrete adjoint), not the
+            # continuous adjoint below, from which it differs at O(1) for one unconverged step per interval
+            adj_y0, grads, status, _nfe, _ns = engine.solve_backprop(
+                p, t64, sol, grad_sol.contiguous(), method, control, per_sample, t_is_f32, want_grads=need_p,
+                max_num_steps=max_steps, stats=bstats, step_size=steps[0], grid_steps=ctx.phx_bp_steps)
+        else:
+            adj_y0, grads, status, _nfe, _ns = engine.solve_adjoint(
+                p, t64, sol, grad_sol.contiguous(), a_method, control, a_rtol, a_atol, per_sample, t_is_f32,
+                want_grads=need_p, max_num_steps=max_steps, stats=bstats, step_size=steps[1])
         # The status read-back is the one host<->device round trip of a training step.  It is queued as an
         # end-of-backward callback of the autograd engine (the mechanism DDP finalises with): the exception still comes
         # out of loss.backward(), but the host returns the gradients and runs its accumulation nodes while the kernel
@@ -199,16 +206,21 @@ class _OdeintAdjointFn(torch.autograd.Function):
 
 def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_stats=False):
     """odeint.py:30-74.  The reference's `odeint` returns an autograd-tracked solution (backpropagation through the
-    solver's own operations).  The fused stepper keeps no such history, so for an ODENet:
-      * nothing requires grad, autograd is off (validation, analysis callers), or `return_stats`: plain forward solve;
-      * something requires grad: the call is routed through `odeint_adjoint`, so the result IS differentiable.  With
-        dopri5 the continuous adjoint agrees with backpropagation through the converged solve to the solver tolerance
-        (<= 2e-6 relative).  With a fixed grid (euler / midpoint / rk4: one step per interval, or
-        the steps of options["step_size"]; not converged in general) the two differ, at O(1) for one step per interval,
-        and returning the adjoint's gradient silently would not be the
-        reference's `odeint`: the BACKWARD pass of such a call raises NotImplementedError (the forward result is
-        exact either way; PHOENIX itself trains through `odeint_adjoint`, train_insilico.py:15-18, which is
-        reproduced operation for operation)."""
+    solver's own operations).  For an ODENet:
+      * nothing requires grad, autograd is off (validation, analysis callers), or `return_stats`: plain forward solve
+        (`return_stats=True` is forward-only: its result carries no autograd history);
+      * something requires grad, euler / midpoint / rk4 (one step per interval, or the steps of options["step_size"]):
+        the result is differentiable by backpropagation through the fixed-grid steps -- the discrete adjoint, computed by
+        one persistent kernel (phx_odeint_backprop_backward): the exact gradient of the numbers the forward pass
+        produced, whatever the step, like the reference's.  `odeint_adjoint` stays the continuous adjoint, which differs
+        from it at O(1) for one unconverged step per interval.  Under a step size the backward pass re-runs the forward
+        grid and keeps the start state of every step (steps x B x N x 4 bytes).  A call whose backward pass could not be
+        served raises RuntimeError HERE, not from backward(): hidden layers over H = 128, PHX_ENGINE=v0, a grid whose
+        checkpoints exceed engine.BACKPROP_MAX_CHECKPOINT_BYTES.  Solver assertions of the forward solve
+        (max_num_steps exceeded) are then raised with the backward's, from backward(), as for `odeint_adjoint`;
+      * something requires grad, dopri5: the call is routed through `odeint_adjoint`; the continuous adjoint agrees with
+        backpropagation through the converged solve to the solver tolerance (<= 2e-6 relative).
+    Gradients with respect to `t` are not computed."""
     y0, t, rtol, atol, method, options = _check_inputs(func, y0, t, rtol, atol, method, options)
     if not _is_odenet(func):      # any other module: unfused torch stepper, differentiable by plain backpropagation
         engine._require_gpu(y0, "y0")          # like every other entry point: no CPU compute path in this package
@@ -303,7 +315,9 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     # be recording AND something must require grad (needs_input_grad mirrors .requires_grad even under no_grad: the
     # reference's validation code calls odeint_adjoint inside torch.no_grad(), train_insilico.py:77-106).
     # (a plain `odeint` call routed here keeps the reference's synchronous asserts: its caller may never run backward)
-    defer = torch.is_grad_enabled() and (y0.requires_grad or any(x.requires_grad for x in params)) and not _via_odeint
+    # ... except with a fixed-grid method, whose backward pass (backpropagation through the steps) reads both together
+    defer = (torch.is_grad_enabled() and (y0.requires_grad or any(x.requires_grad for x in params)) and
+             (not _via_odeint or adjoint_method in _FIXED_GRID_METHODS))
     cfg = (method, control, rtol, atol, per_sample, t_is_f32, int(options.get("max_num_steps", 0)),
            (adjoint_method, float(adjoint_rtol), float(adjoint_atol), bool(_via_odeint)), defer,
            (options.get("step_size", 0.0), _adjoint_step(options, a_step, adjoint_method)))
