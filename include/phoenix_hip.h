@@ -76,7 +76,8 @@ typedef struct phx_solve_opts {
     int method;         /* phx_method */
     int control;        /* phx_control */
     double rtol, atol;  /* odeint defaults 1e-7 / 1e-9 (odeint.py:30) */
-    int t_per_sample;   /* 0: t is [T] shared;  1: t is [B, T] (training loop: t[b] = (t_i, t_{i+1})) */
+    int t_per_sample;   /* 0: t is [T] shared;  1: t is [B, T] (training loop: t[b] = (t_i, t_{i+1})); with PHX_CTRL_SHARED
+                           and calls > 1 (phx_odeint only): t is [calls, T], one grid per call */
     int t_is_f32;       /* 1: the caller's t tensor was float32 (fixed-grid dt is then formed in fp32);
                            2: ... and the buffer passed as `t` still holds float32 values (no conversion) */
     long long max_num_steps; /* <=0: 2^31-1 like the reference (rk_common.py:110) */
@@ -114,6 +115,19 @@ int phx_layout_params(const float *Ws, const float *Wp, const float *Wa, const f
                       void *wimg_out, void *stream);
 /* ... for phx_odeint with opts->calls = calls (0: this batch of calls cannot be planned, solve the calls one by one) */
 size_t phx_odeint_calls_workspace_bytes(int N, int H, int B, int T, int calls);
+/* Calls with a time grid of their own: phx_odeint with PHX_CTRL_SHARED, opts->calls = calls > 1 AND opts->t_per_sample = 1
+ * takes t as [calls, T], row g the grid of call g (rows [g * B/calls, (g + 1) * B/calls) of y0 / sol / status); a row may
+ * increase or decrease whatever its neighbours do, opts->t_is_f32 = 2 holds as for any t.  The loop of validation()
+ * (train_insilico.py:77-106: one odeint per validation item over that item's own times) in a few launches.  A call that
+ * fails (status != 0 on all of its rows, NaN in the outputs it never reached) does not touch the other calls.  dopri5
+ * runs on k1_solve_fwd3 / k1_solve_fwd3c where they plan one call (batch group g = call g), every other case on
+ * k1_solve_fwd; a launch takes as many calls as have all their workgroups resident (TG * G <= CUs), the shared chunk
+ * driver walks the rest.  calls <= 1 with t_per_sample under shared control stays PHX_ERR_BAD_ARG, and so does any
+ * t_per_sample under shared control in phx_odeint_stepped with a step size and in the backward entry points.
+ * phx_odeint_calls_grids_workspace_bytes: the workspace of that form (0: no kernel plans a call of B/calls rows -- more
+ * than 256 rows of dopri5 beyond the first-generation kernel's 512, PHX_ENGINE=v0: solve the calls one by one).  Unlike
+ * phx_odeint_calls_workspace_bytes it depends on the method, and it sizes for 256 CUs when no device is visible. */
+size_t phx_odeint_calls_grids_workspace_bytes(int N, int H, int B, int T, int calls, int method);
 
 /* Replaces ODENet.forward / prior_only_forward (odenet.py:85-98): out[B,N] = f(y[B,N]). */
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only,
@@ -285,6 +299,16 @@ int phx_debug_forward_kernel_m(int N, int H, int B, int T, int control, int meth
  * residency is walked in chunks: e.g. 256 B-cell trajectories = two launches of k1_solve_adj3c).  op = PHX_OP_ODEINT or
  * PHX_OP_ADJOINT; 0 when no plan exists.  bench.py multiplies per-launch profile figures with it. */
 int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, int method);
+/* Diagnostic only, the calls-with-their-own-grids form of phx_odeint (B rows = `calls` calls of B / calls rows):
+ * phx_debug_calls_grids_kernel_m: the kernel that serves it, numbered as by phx_debug_forward_kernel_m (1, 3 or 4; 0: none,
+ *   the call returns PHX_ERR_BAD_ARG).
+ * phx_debug_calls_grids_plan: returns the calls ONE launch takes (0: none) and, when `plan` is non-NULL, writes plan[0..5] =
+ *   kernel, TG (batch groups = calls per launch), G (workgroups per group), NW (waves per workgroup), trajectory tiles per
+ *   group, and the CU count the plan was sized for: TG * G <= plan[5] always.
+ * phx_debug_calls_grids_launches: ceil(calls / calls per launch), the launches one phx_odeint call makes (0: none). */
+int phx_debug_calls_grids_kernel_m(int N, int H, int B, int T, int calls, int method);
+int phx_debug_calls_grids_plan(int N, int H, int B, int T, int calls, int method, int *plan);
+int phx_debug_calls_grids_launches(int N, int H, int B, int T, int calls, int method);
 
 #ifdef __cplusplus
 }

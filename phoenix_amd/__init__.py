@@ -5,7 +5,7 @@ replaces `from torchdiffeq import odeint_adjoint as odeint` (train_insilico.py:1
 from .odeint import SOLVERS, odeint, odeint_adjoint, odeint_calls, odeint_per_sample  # noqa: F401
 from .odenet import ODENet  # noqa: F401
 from .engine import check_pending_status, set_status_mode  # noqa: F401
-from .training import training_step  # noqa: F401
+from .training import get_true_val_set_r2, my_r_squared, training_step, validation  # noqa: F401
 from .graphs import GraphedStep  # noqa: F401
 from .data import DataHandler, readcsv, writecsv  # noqa: F401
 from .prior import PriorMatrix, prior_targets, read_prior_matrix  # noqa: F401

@@ -32,7 +32,9 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_debug_adjoint_kernel_m", "phx_prior_z_bytes", "phx_prior_mse_save", "phx_prior_vjp_saved",
            "phx_layout_params", "phx_debug_forward_kernel_m", "phx_debug_queue_kernel_events", "phx_debug_solve_launches",
            "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped", "phx_odeint_backprop_backward",
-           "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches")
+           "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
+           "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
+           "phx_debug_calls_grids_launches")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -101,6 +103,11 @@ def load():
     lib.phx_debug_adjoint_kernel_m.argtypes = [C.c_int] * 6
     lib.phx_odeint_calls_workspace_bytes.argtypes = [C.c_int] * 5
     lib.phx_odeint_calls_workspace_bytes.restype = C.c_size_t
+    lib.phx_odeint_calls_grids_workspace_bytes.argtypes = [C.c_int] * 6
+    lib.phx_odeint_calls_grids_workspace_bytes.restype = C.c_size_t
+    lib.phx_debug_calls_grids_kernel_m.argtypes = [C.c_int] * 6
+    lib.phx_debug_calls_grids_plan.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int)]
+    lib.phx_debug_calls_grids_launches.argtypes = [C.c_int] * 6
     lib.phx_weight_image_bytes.argtypes = [C.c_int, C.c_int]
     lib.phx_weight_image_bytes.restype = C.c_size_t
     lib.phx_pack_weight_images.argtypes = [C.POINTER(PhxParams), vp, vp]

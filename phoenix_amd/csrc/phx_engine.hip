@@ -813,12 +813,13 @@ inline int solve_ht(int HC, int Hc) { return Hc <= 48 ? 3 : ((HC > 1 && Hc <= 11
 
 // picks (NW, TPW, NB): minimise the per-wave MFMA work TPW*NB subject to LDS and residency
 bool plan_v1(int N, int H, int B, int T, int control, int nvec, int fwidth /* hidden frag tiles / HT */,
-             size_t lds_per_block_extra, D1 *out, size_t ctl_extra_per_traj = 0, int nw_cap = 8, int calls = 1)
+             size_t lds_per_block_extra, D1 *out, size_t ctl_extra_per_traj = 0, int nw_cap = 8, int calls = 1,
+             int cus_given = 0 /* > 0: plan for this many CUs instead of the current device's */)
 {
     // calls > 1 (shared control only): B = calls x Bcall rows, one batch group per call
     if (calls > 1 && (control != PHX_CTRL_SHARED || B % calls != 0)) return false;
     const int Bcall = calls > 1 ? B / calls : 0;
-    const int cus = num_cus();
+    const int cus = cus_given > 0 ? cus_given : num_cus();
     if (cus <= 0 || force_v0()) return false;
     // H > 128: the hidden layer is cut into HC chunks of Hc <= 128 rows whose weights take turns in LDS
     const int HC = (H + 127) / 128, Hc = (H + HC - 1) / HC;
@@ -877,6 +878,38 @@ int pick_calls_v1(int N, int H, int B, int T, int calls)
     for (int n = std::min(calls, std::max(1, num_cus())); n >= 1; --n)
         if (plan_v1(N, H, n * Bcall, T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, &d1, 0, 8, n)) return n;
     return 0;
+}
+
+// ... where every call has a time grid of its own (phx_solve_opts.t_per_sample under shared control): the first of
+// k1_solve_fwd3, k1_solve_fwd3c (dopri5) and k1_solve_fwd that plans a call, and the largest number of calls one launch of
+// it takes (every workgroup resident: TG * G <= cus).  cus <= 0: sized for 256 CUs (no device in sight).
+const Backend &v1_fwd_backend();
+struct CallsPick {
+    const Backend *be;   // null: no kernel plans a call of this shape
+    int n;               // calls per launch
+    int cus;
+};
+bool plan_calls(const CallsPick &k, int N, int H, int Bcall, int n, int T, D1 *d)
+{
+    if (k.be == &fwd3_backend()) return plan_fwd3_calls(k.cus, N, H, Bcall, n, T, d);
+    if (k.be == &fwd3c_backend()) return plan_fwd3c_calls(k.cus, N, H, Bcall, n, T, d);
+    return plan_v1(N, H, n * Bcall, T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, d, 0, 8, n, k.cus);
+}
+CallsPick pick_calls_grids(int cus, int N, int H, int Bcall, int calls, int T, int method)
+{
+    if (cus <= 0) cus = 256;
+    if (N <= 0 || H <= 0 || Bcall <= 0 || calls < 1 || method < PHX_EULER || method > PHX_DOPRI5) return {nullptr, 0, cus};
+    const Backend *const list[] = {&fwd3_backend(), &fwd3c_backend(), &v1_fwd_backend()};
+    for (const Backend *be : list) {
+        if (be->id != 1 && method != PHX_DOPRI5) continue;
+        const CallsPick k{be, 0, cus};
+        D1 d;
+        if (!plan_calls(k, N, H, Bcall, 1, T, &d)) continue;
+        for (int n = std::min(calls, cus); n > 1; --n)
+            if (plan_calls(k, N, H, Bcall, n, T, &d)) return {be, n, cus};
+        return {be, 1, cus};
+    }
+    return {nullptr, 0, cus};
 }
 
 bool plan_v1_fwd(int N, int H, int B, int T, int control, int /* method: any */, D1 *out)
@@ -1047,6 +1080,7 @@ struct SolveCall {
     double step = 0.0;   // SolveCfg::step
     int control = -1;    // >= 0: the step control the launches are planned and run with instead of o->control
     float *ckpt = nullptr;   // k1_solve_bp: the checkpoint region behind the launches' layouts
+    int Bcall = 0;       // > 0 with o->t_per_sample: t is [calls, T], one row per call of Bcall trajectories
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1088,7 +1122,7 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
         auto rows = [&](auto *q) { return q ? q + r0 : q; };
         a.t = !o->t_per_sample ? c.t   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
               : reinterpret_cast<const double *>(reinterpret_cast<const char *>(c.t) +
-                                                 (size_t)b0 * c.T * (o->t_is_f32 == 2 ? 4 : 8));
+                                                 (size_t)(c.Bcall > 0 ? b0 / c.Bcall : b0) * c.T * (o->t_is_f32 == 2 ? 4 : 8));
         a.y0 = rows(c.y0); a.sol = rows(c.sol);
         a.y_saved = rows(c.y_saved); a.grad_y = rows(c.grad_y); a.adj_y0 = rows(c.adj_y0);
         a.status = c.status + b0; a.nfe = c.nfe + b0; a.nsteps = c.nsteps + b0;
@@ -1712,6 +1746,46 @@ size_t phx_odeint_calls_workspace_bytes(int N, int H, int B, int T, int calls)
     return layout_v1_fwd(d1, false).total;
 }
 
+int phx_debug_calls_grids_plan(int N, int H, int B, int T, int calls, int method, int *plan)
+{
+    if (plan)
+        for (int i = 0; i < 6; ++i) plan[i] = 0;
+    if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return 0;
+    const CallsPick k = pick_calls_grids(num_cus(), N, H, B / calls, calls, T, method);
+    D1 d;
+    if (!k.be || !plan_calls(k, N, H, B / calls, k.n, T, &d)) return 0;
+    if (plan) {
+        plan[0] = k.be->id; plan[1] = d.TG; plan[2] = d.G; plan[3] = d.NW; plan[4] = d.ntg; plan[5] = k.cus;
+    }
+    return k.n;
+}
+
+int phx_debug_calls_grids_kernel_m(int N, int H, int B, int T, int calls, int method)
+{
+    int plan[6];
+    return phx_debug_calls_grids_plan(N, H, B, T, calls, method, plan) > 0 ? plan[0] : 0;
+}
+
+int phx_debug_calls_grids_launches(int N, int H, int B, int T, int calls, int method)
+{
+    const int n = phx_debug_calls_grids_plan(N, H, B, T, calls, method, nullptr);
+    return n > 0 ? (calls + n - 1) / n : 0;
+}
+
+size_t phx_odeint_calls_grids_workspace_bytes(int N, int H, int B, int T, int calls, int method)
+{
+    if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return 0;
+    const int Bc = B / calls;
+    const CallsPick k = pick_calls_grids(num_cus(), N, H, Bc, calls, T, method);
+    if (!k.be) return 0;
+    size_t need = 0;
+    for (const int n : {k.n, calls % k.n}) {   // the launches of k.n calls and the remainder launch
+        D1 d;
+        if (n > 0 && plan_calls(k, N, H, Bc, n, T, &d)) need = std::max(need, k.be->layout(d, false).total);
+    }
+    return need;
+}
+
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,
                     size_t workspace_bytes, void *stream)
 {
@@ -1864,7 +1938,8 @@ int phx_odeint_stepped(const phx_params *p, const float *y0_all, const double *t
         T < 1 || !workspace)
         return PHX_ERR_BAD_ARG;
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
-    if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
+    // a shared controller has one time grid -- unless the batch is several calls: then one row of t per call
+    if (o->control == PHX_CTRL_SHARED && o->t_per_sample && o->calls <= 1) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
                 workspace, workspace_bytes, st};
@@ -1882,6 +1957,15 @@ int phx_odeint_stepped(const phx_params *p, const float *y0_all, const double *t
     // calls as there are batch groups to run them (first-generation kernel only)
     if (o->calls > 1) {
         if (o->control != PHX_CTRL_SHARED || B % o->calls != 0) return PHX_ERR_BAD_ARG;
+        if (o->t_per_sample) {   // a time grid per call: the dopri5 kernels of the third generation where they plan the call
+            const int cus = num_cus();
+            if (cus <= 0) return PHX_ERR_LAUNCH;
+            const int Bc = B / o->calls;
+            const CallsPick k = pick_calls_grids(cus, p->N, p->H, Bc, o->calls, T, o->method);
+            if (!k.be) return PHX_ERR_BAD_ARG;
+            c.Bcall = Bc;
+            return run_solve(*k.be, k.n * Bc, [&](int bc, D1 *d) { return plan_calls(k, p->N, p->H, Bc, bc / Bc, T, d); }, c);
+        }
         const int Bcall = B / o->calls, chunk = pick_calls_v1(p->N, p->H, B, T, o->calls) * Bcall;
         if (chunk == 0) return PHX_ERR_BAD_ARG;
         return run_solve(v1_fwd_backend(), chunk, [&](int bc, D1 *d) {

@@ -26,13 +26,15 @@ bool fwd3_disabled()
 
 // (NW, TPW, NB) as plan_v1 picks them for the forward kernel: per-SIMD MFMA work first, then two waves per SIMD, then
 // the smallest batch group
-bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
+// calls > 1 (shared control): B = calls x Bcall rows, one batch group per call (plan_v1's rule: D1::Bcall)
+bool plan_fwd3_cus(int cus, int N, int H, int B, int T, int control, int method, int calls, D1 *out)
 {
-    const int cus = num_cus();
     if (cus <= 0 || fwd3_disabled() || method != PHX_DOPRI5 || H > 48) return false;
+    if (calls > 1 && (control != PHX_CTRL_SHARED || B % calls != 0)) return false;
+    const int Bcall = calls > 1 ? B / calls : 0;
     const int HT = 3;
     const size_t blkbytes = (size_t)blk_floats_ch(HT, H) * 4;
-    const int nblk = (N + 31) / 32, ntt = (B + 15) / 16;
+    const int nblk = (N + 31) / 32, ntt = ((Bcall ? Bcall : B) + 15) / 16;
     long long best_cost = -1;
     D1 best{};
     // One wave per SIMD (NW <= 4).  The eight-wave form (two waves per SIMD under a 256-register cap) computed wrong step
@@ -43,10 +45,11 @@ bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
     if (const char *e = getenv("PHX_V1_MAXNW")) nwmax = std::min(nwmax, std::max(1, atoi(e)));
     for (int NW = nwmax; NW >= 1; NW >>= 1)
         for (int TPW = 1; TPW <= 4; TPW <<= 1) {
-            const int slots = NW * TPW, TG = (ntt + slots - 1) / slots;
-            const int ntg = TG == 1 ? std::min(slots, ntt) : slots, Bt = 16 * ntg;
+            const int slots = NW * TPW, TG = Bcall ? calls : (ntt + slots - 1) / slots;
+            if (Bcall && slots < ntt) continue;   // a call is one group
+            const int ntg = (TG == 1 || Bcall) ? std::min(slots, ntt) : slots, Bt = 16 * ntg;
             const bool helpers = ntg < slots;
-            if (control == PHX_CTRL_SHARED && TG != 1) continue;
+            if (control == PHX_CTRL_SHARED && TG != 1 && !Bcall) continue;
             // (+ the LDS of the block-split combine where the batch is that small: v3_split_parts)
             const size_t cb = ((ctlf3_bytes(Bt, ntg) + 15) & ~(size_t)15) +
                               (v3_split_parts(TG, NW, TPW, ntg) > 1 ? v3_comb_bytes(NW, 2 * HT) : 0);
@@ -63,7 +66,7 @@ bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
                     best.N = N; best.H = H; best.B = B; best.T = T; best.HT = HT; best.NB = NB; best.NW = NW;
                     best.TPW = TPW; best.G = G; best.TG = TG; best.nblk = nblk; best.ntg = ntg; best.Bt = Bt;
                     best.nvec = NVEC_FWD3; best.BN = (long long)B * N; best.HC = 1; best.Hc = H;
-                    best.Bcall = 0; best.cntN = (long long)B * N;
+                    best.Bcall = Bcall; best.cntN = (long long)(Bcall ? Bcall : B) * N;
                 }
                 break;  // smallest feasible NB for this (NW, TPW) is the cheapest
             }
@@ -71,6 +74,11 @@ bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
     if (best_cost < 0) return false;
     *out = best;
     return true;
+}
+
+bool plan_fwd3(int N, int H, int B, int T, int control, int method, D1 *out)
+{
+    return plan_fwd3_cus(num_cus(), N, H, B, T, control, method, 1, out);
 }
 
 Regions make_layout_f3(const D1 &d, bool)
@@ -109,6 +117,9 @@ const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
     const char *eh = getenv("PHX_V3_HALF");   // diagnostic: 0 = full last tile also where half of it is padding
     const bool half = p->H <= 16 * (d.HT - 1) + 8 && !(eh && eh[0] == '0');
     const bool split = v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1;   // small batch: the waves of a tile split its blocks
+    if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
+        return half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false, true>)
+                    : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, false, true>);
     return split ? (half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, true>)
                          : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, true>))
                  : (half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false>)
@@ -128,5 +139,9 @@ const Backend &fwd3_backend()
 {
     static const Backend b = {3, true, false, true, plan_fwd3, make_layout_f3, plan6_ht, prepare_fwd3, launch_fwd3, nullptr};
     return b;
+}
+bool plan_fwd3_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out)
+{
+    return plan_fwd3_cus(cus, N, H, Bcall * calls, T, PHX_CTRL_SHARED, PHX_DOPRI5, calls, out);
 }
 }  // namespace phxh

@@ -37,13 +37,15 @@ int env_int(const char *name, int dflt)
 // keeps their partial sums in registers); all chunks LDS resident when they fit, else one re-staged slot.  Cost: the
 // per-wave MFMA work first, then the exchange volume (members per group).  A plan of ONE slot per wave whose workgroups
 // leave half the chip idle takes HALF-BLOCK gene tiles (hb: twice the workgroups, half the sweep work each).
-bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
+// calls > 1 (shared control): B = calls x Bcall rows, one batch group per call (plan_v1's rule: D1::Bcall)
+bool plan_fwd3c_cus(int cus, int N, int H, int B, int T, int control, int method, int calls, D1 *out)
 {
-    const int cus = num_cus();
     if (cus <= 0 || fwd3c_disabled() || method != PHX_DOPRI5 || H <= 48 || H > 256) return false;
+    if (calls > 1 && (control != PHX_CTRL_SHARED || B % calls != 0)) return false;
+    const int Bcall = calls > 1 ? B / calls : 0;
     const int HT = 3, HC = (H + 47) / 48, Hc = (H + HC - 1) / HC;
     const size_t blkbytes = (size_t)blk_floats_ch(HT, Hc) * 4;
-    const int nblk = (N + 31) / 32, ntt = (B + 15) / 16;
+    const int nblk = (N + 31) / 32, ntt = ((Bcall ? Bcall : B) + 15) / 16;
     const int fnb = env_int("PHX_V3C_NB", 0), ftpw = env_int("PHX_V3C_TPW", 0), fres = env_int("PHX_V3C_RES", -1);
     const int fhb = env_int("PHX_V3C_HB", -1);
     long long best_cost = -1;
@@ -59,7 +61,10 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
             // helper waves (measured, round 5: -8 ... -32 % of a launch; 23 yeast pairs as two groups of one tile: neutral).
             // PHX_V3C_NTG forces the tiles per group (4: the plan before this rule).
             const int fntg = env_int("PHX_V3C_NTG", 0);
-            if (fntg > 0 && fntg <= slots) { ntg = std::min(fntg, ntt); TG = (ntt + ntg - 1) / ntg; }
+            if (Bcall) {   // a call is one group
+                if (slots < ntt) continue;
+                TG = calls; ntg = ntt;
+            } else if (fntg > 0 && fntg <= slots) { ntg = std::min(fntg, ntt); TG = (ntt + ntg - 1) / ntg; }
             else if (fntg == 0 && TPW == 1 && control != PHX_CTRL_SHARED) {
                 // (one-tile groups may take three quarters of the chip, two-tile groups half of it: beyond, the forward
                 // launch measured +8 ... +18 % -- 252 half-block workgroups at two tiles per group -- where the backward gains)
@@ -73,7 +78,7 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
             // than the workgroup has threads (eight-tile waves, more than 16 tiles) would leave the rest unsolved
             if (Bt > 64 * NW) continue;
             const bool helpers = ntg < slots;
-            if (control == PHX_CTRL_SHARED && TG != 1) continue;
+            if (control == PHX_CTRL_SHARED && TG != 1 && !Bcall) continue;
             const size_t cb = ctlf3c_bytes(Bt, ntg);
             for (int NB = 1; NB <= 8 && TPW * NB <= 8; NB <<= 1) {
                 if (fnb > 0 && NB != fnb) continue;
@@ -88,7 +93,7 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
                     best.N = N; best.H = H; best.B = B; best.T = T; best.HT = HT; best.NB = NB; best.NW = NW;
                     best.TPW = TPW; best.G = G; best.TG = TG; best.nblk = nblk; best.ntg = ntg; best.Bt = Bt;
                     best.nvec = NVEC_FWD3C; best.BN = (long long)B * N; best.HC = HC; best.Hc = Hc;
-                    best.Bcall = 0; best.cntN = (long long)B * N; best.res = res ? 1 : 0;
+                    best.Bcall = Bcall; best.cntN = (long long)(Bcall ? Bcall : B) * N; best.res = res ? 1 : 0;
                     const int nslot = TPW * NB;
                     // measured (round 5, H = 120 / 200, 8..220 gene blocks, 16..128 trajectories): -9..-33 % of a launch while
                     // the groups' rows times their workgroups stay small (four-tile groups on at most half the chip, one-tile
@@ -109,6 +114,11 @@ bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
     if (best.hb) best.G = 2 * best.nblk;
     *out = best;
     return true;
+}
+
+bool plan_fwd3c(int N, int H, int B, int T, int control, int method, D1 *out)
+{
+    return plan_fwd3c_cus(num_cus(), N, H, B, T, control, method, 1, out);
 }
 
 
@@ -148,6 +158,15 @@ const void *prepare_fwd3c(SolveArgs &a, const phx_params *p, hipStream_t st)
     // (tile, block) slots per wave the kernel is built for (unused slots of the eight-slot form cost a scalar branch each)
     const int nbt = d.TPW * d.NB <= 1 || d.split > 1 ? 1 : 8;
     const bool half = d.Hc <= 40;   // every chunk's last tile has at most 8 live rows (rho16, phx_mfma_v3common.inc)
+    if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
+        switch (nbt * 2 + (half ? 1 : 0) + (d.hb ? 32 : 0)) {
+        case 35: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, true, true>);
+        case 34: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, false, true, true>);
+        case 3: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, false, true>);
+        case 2: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, false, false, true>);
+        case 17: return reinterpret_cast<const void *>(k1_solve_fwd3c<8, true, false, true>);
+        default: return reinterpret_cast<const void *>(k1_solve_fwd3c<8, false, false, true>);
+        }
     switch (nbt * 2 + (half ? 1 : 0) + (d.hb ? 32 : 0)) {
     case 35: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, true>);
     case 34: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, false, true>);
@@ -172,5 +191,9 @@ const Backend &fwd3c_backend()
     static const Backend b = {4, true, false, true,
                                     plan_fwd3c, make_layout_f3c, plan6_chunked, prepare_fwd3c, launch_fwd3c, nullptr};
     return b;
+}
+bool plan_fwd3c_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out)
+{
+    return plan_fwd3c_cus(cus, N, H, Bcall * calls, T, PHX_CTRL_SHARED, PHX_DOPRI5, calls, out);
 }
 }  // namespace phxh

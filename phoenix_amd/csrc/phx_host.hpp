@@ -213,6 +213,10 @@ const Backend &fwd3c_backend();
 const Backend &adj2_backend();
 const Backend &adj3_backend();
 const Backend &adj3c_backend();
+// `calls` independent shared-control dopri5 calls of Bcall rows in ONE launch of k1_solve_fwd3 / k1_solve_fwd3c (D1::Bcall:
+// batch group g = call g); calls == 1: the ordinary one-group plan.  `cus`: the CU count the plan keeps TG * G within.
+bool plan_fwd3_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out);
+bool plan_fwd3c_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out);
 // k1_solve_bp (backpropagation through the fixed-grid steps): not in the lists of the adjoint direction, it has entry
 // points of its own.  bp_chunk: rows per launch of a batch (0: no plan); bp_base_bytes: workspace in front of the
 // checkpoint region; both size for 256 CUs when cus <= 0 (no device in sight).

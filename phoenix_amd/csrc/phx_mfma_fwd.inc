@@ -68,7 +68,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
     for (int lb = tid; lb < Bt; lb += blockDim.x) {
         const int b = rowof(lb);
         const bool vb = b < B;
-        const int cbsrc = shared ? 0 : (vb ? b : 0);
+        const int cbsrc = shared ? grp : (vb ? b : 0);
         const TimeRow tb = trowT(t, T, cfg, cbsrc);
         float sg = 1.0f;
         int st = PHX_OK;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
     auto dt_of = [&](int lb, int i) -> float {   // fixed-grid dt of interval i (solvers.py:85-87)
         if (stepped) return c.dtf[lb];           // ... or of the trajectory's running grid step
         const int b = rowof(lb);
-        const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+        const TimeRow tb = trowT(t, T, cfg, shared ? grp : min(b, B - 1));
         const double sg = (double)c.sgn[lb];
         const double s0 = sg * tb[i], s1 = sg * tb[i + 1];
         return cfg.t_is_f32 ? ((float)s1 - (float)s0) : (float)(s1 - s0);
@@ -489,7 +489,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
         for (int lb = tid; lb < Bt; lb += blockDim.x) {
             c.dtf[lb] = 0.f;
             if (c.done[lb]) continue;
-            const TimeRow tb = trowT(t, T, cfg, shared ? 0 : rowof(lb));
+            const TimeRow tb = trowT(t, T, cfg, shared ? grp : rowof(lb));
             const double sg = (double)c.sgn[lb];
             c.nsiv[lb] = step_grid_steps(sg * tb[0], sg * tb[T - 1], cfg.step, tf32);
             // max_num_steps: a budget of grid steps per call (a tiny step would hold the device for hours otherwise)
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
         while (active > 0 && !x.aborted) {
             for (int lb = tid; lb < Bt; lb += blockDim.x) {
                 if (c.done[lb]) continue;
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : rowof(lb));
+                const TimeRow tb = trowT(t, T, cfg, shared ? grp : rowof(lb));
                 const double sg = (double)c.sgn[lb];
                 const int k = c.nsteps[lb], n = c.nsiv[lb];
                 const double g0 = c.rk_t1[lb];
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
                 const int lo = c.out_lo[lb], hi = c.out_hi[lb];
                 const double g0 = c.rk_t0[lb], g1 = c.rk_t1[lb];
                 const double sg = (double)c.sgn[lb];
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+                const TimeRow tb = trowT(t, T, cfg, shared ? grp : min(b, B - 1));
                 for (int bl = 0; bl < nbl; ++bl) {
                     float yv[8], y1[8], k0[8], k1[8], k2[8], k3[8];
                     load8(tptr(V_Y0, ttl, bl), yv);
@@ -632,7 +632,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
             if (tid < Bt && !c.done[tid]) {
                 const int lb = tid;
                 const int b = rowof(lb);
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                const TimeRow tb = trowT(t, T, cfg, shared ? grp : b);
                 const double sg = (double)c.sgn[lb];
                 const float ratio = nv[0];
                 const int acc = (ratio <= 1.0f) ? 1 : 0;
@@ -681,7 +681,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd(Net net, D1 d, W1 w, SolveC
                 const double t0 = c.rk_t0[lb], t1 = c.rk_t1[lb];
                 const float dts = c.dtp[lb];
                 const double sg = (double)c.sgn[lb];
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+                const TimeRow tb = trowT(t, T, cfg, shared ? grp : min(b, B - 1));
                 for (int bl = 0; bl < nbl; ++bl) {
                     if (!__any(adv)) continue;
                     float y0v[8], y1v[8], f0[8], f1[8];

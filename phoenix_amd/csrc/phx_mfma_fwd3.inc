@@ -18,7 +18,10 @@ constexpr int NVEC_FWD3 = 8;
 
 __host__ __device__ inline size_t ctlf3_bytes(int Bt, int ntg) { return ctl_bytes(Bt) + (size_t)ntg * 8 + 64; }
 
-template <int HT, int MAXT, bool HALF, bool SPLIT>
+// CALLS: the launch is d.TG independent odeint calls of d.Bcall rows under shared control (D1::Bcall, phx_solver.hpp):
+// batch group g is call g, it reads time row g when cfg.t_per_sample is set, and the rows of its last tile beyond
+// d.Bcall are padding (rowof).  A template flag, so that the instantiations of every other launch compile as before.
+template <int HT, int MAXT, bool HALF, bool SPLIT, bool CALLS = false>
 __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, SolveCfg cfg, const float *__restrict__ y0,
                                                       const double *__restrict__ t, float *sol, int *status,
                                                       int *nfe_out, int *nsteps_out)
@@ -31,6 +34,9 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     const int nbl = min(d.NB, d.nblk - blk0);
     const int N = d.N, B = d.B, T = d.T, Bt = d.Bt, ntg = d.ntg, G = d.G;
     const bool shared = cfg.control == PHX_CTRL_SHARED;
+    // the caller's row of local row lb (B: none, a padding row), and the time row of a shared-control group
+    auto rowof = [&](int lb) -> int { return CALLS ? (lb < d.Bcall ? grp * d.Bcall + lb : B) : grp * Bt + lb; };
+    const int trow_sh = CALLS ? grp : 0;
     constexpr int F2 = 2 * HT;
     // small batches: the waves of a tile split its gene blocks (v3_split_parts, phx_mfma_v3common.inc)
     // (SPLIT is a template flag: the large-batch instantiation compiles exactly as without this path -- as run-time branches it cost
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     constexpr int NBX = 8;   // plan_fwd3 never gives a workgroup more gene blocks
     float xinit[NBX][8];
     {
-        const int ttl = wtile, b = grp * Bt + ttl * 16 + li;
+        const int ttl = wtile, b = rowof(ttl * 16 + li);
 #pragma unroll
         for (int bl = 0; bl < NBX; ++bl)
             if (bl >= b_lo && bl < b_hi && ttl < ntg) row_load8(y0, (long long)b * N, (blk0 + bl) * 32 + gmap(lq, 0), N, b < B, 0.5f, xinit[bl]);
@@ -93,9 +99,9 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
 
     // ---- controllers (replicated in every workgroup of the group; deterministic => identical)
     for (int lb = tid; lb < Bt; lb += blockDim.x) {
-        const int b = grp * Bt + lb;
+        const int b = rowof(lb);
         const bool vb = b < B;
-        const TimeRow tb = trowT(t, T, cfg, shared ? 0 : (vb ? b : 0));
+        const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : (vb ? b : 0));
         float sg = 1.0f;
         int st = PHX_OK;
         if (T >= 2) {
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     for (int i = tid; i < ntg; i += blockDim.x) { kbs[i] = 0; rotf[i] = 0; }
     // ---- initial state: Y0 tiles <- y0, sol[0] <- y0
     {
-        const int ttl = wtile, b = grp * Bt + ttl * 16 + li;
+        const int ttl = wtile, b = rowof(ttl * 16 + li);
 #pragma unroll
         for (int bl = 0; bl < NBX; ++bl)
             if (bl >= b_lo && bl < b_hi && ttl < ntg) {
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     for (int s = 1; s < d.TPW; ++s) {
         const int ttl = wtile + s;
         if (ttl >= ntg) continue;
-        const int b = grp * Bt + ttl * 16 + li;
+        const int b = rowof(ttl * 16 + li);
         for (int bl = 0; bl < nbl; ++bl) {
             float xv[8];
             const int g0 = (blk0 + bl) * 32 + gmap(lq, 0);
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
         }
         __syncthreads();
         double v2[2] = {0.0, 0.0};
-        if (tid < Bt && (grp * Bt + tid) < B)
+        if (tid < Bt && rowof(tid) < B)
             for (int k = 0; k < nslots; ++k) v2[k] = (double)c.nrm[(tid >> 4) * 64 + k * 16 + (tid & 15)];
         if (!shared) {
             for (int k = 0; k < nslots; ++k) out[k] = sqrtf((float)(v2[k] / (double)N));
@@ -313,7 +319,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const int ttl = wtile + s;
             if (ttl >= ntg) continue;   // helper wave: no trajectory tile of its own, it only serves the exchange
             const int lb = ttl * 16 + li;
-            const int b = grp * Bt + lb;
+            const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
             float ty0[8], tk[NKL][8];
             auto issue = [&](int bl) {
@@ -566,7 +572,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const int ttl = wtile + s;
             if (ttl >= ntg) continue;
             const int lb = ttl * 16 + li;
-            const int b = grp * Bt + lb;
+            const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
             const bool rot = __builtin_amdgcn_readfirstlane(rotf[ttl]) != 0;
             const bool adv = !c.done[lb] && c.accept[lb];
@@ -575,7 +581,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const double t0 = c.rk_t0[lb], t1 = c.rk_t1[lb];
             const float dts = c.dtp[lb];
             const double sg = (double)c.sgn[lb];
-            const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+            const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : min(b, B - 1));
             const bool outs = __any(adv && hi > lo);
             // two sets of tile registers: the next block's seven tiles are requested before this block's are consumed
             // (the loop is otherwise one exposed load latency per block: its stores may alias the next loads)
@@ -697,8 +703,8 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             // ---- controller (rk_common.py:150-220)
             if (tid < Bt && !c.done[tid]) {
                 const int lb = tid;
-                const int b = grp * Bt + lb;
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                const int b = rowof(lb);
+                const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : b);
                 const double sg = (double)c.sgn[lb];
                 const float ratio = nv[0];
                 const int acc = (ratio <= 1.0f) ? 1 : 0;
@@ -767,7 +773,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
         const int ttl = wtile + s;
         if (ttl >= ntg) continue;
         const int lb = ttl * 16 + li;
-        const int b = grp * Bt + lb;
+        const int b = rowof(lb);
         if (b < B && T >= 2 && (c.st[lb] != PHX_OK || x.aborted))
             for (int bl = b_lo; bl < b_hi; ++bl)
                 for (int jo = max(c.out_idx[lb], 1); jo < T; ++jo)
@@ -779,7 +785,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     }
     if (gt == 0)
         for (int lb = tid; lb < Bt; lb += blockDim.x) {
-            const int b = grp * Bt + lb;
+            const int b = rowof(lb);
             if (b < B) {
                 status[b] = x.aborted ? (int)PHX_ERR_SYNC_TIMEOUT : c.st[lb];
                 nfe_out[b] = c.nfe[lb];

@@ -31,7 +31,8 @@ __host__ __device__ inline size_t hsf_offset(int Bt, int ntg) { return (ctlf3c_b
 // [(part - 1) ntg + tile][2 HT accumulators + one norm row][64] in the same place
 __host__ __device__ inline size_t spf_bytes(int ntg, int parts) { return (size_t)(parts - 1) * ntg * (2 * 3 * 1024 + 256); }
 
-template <int NBT, bool HALF, bool HB>
+// CALLS: as in k1_solve_fwd3 -- d.TG independent shared-control calls of d.Bcall rows, one batch group and one time row each
+template <int NBT, bool HALF, bool HB, bool CALLS = false>
 __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, SolveCfg cfg, const float *__restrict__ y0,
                                                       const double *__restrict__ t, float *sol, int *status,
                                                       int *nfe_out, int *nsteps_out)
@@ -52,6 +53,8 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
     const int N = d.N, B = d.B, T = d.T, Bt = d.Bt, ntg = d.ntg, G = d.G, HC = d.HC;
     const int BLKF = blk_floats_ch(HT, d.Hc);
     const bool shared = cfg.control == PHX_CTRL_SHARED;
+    auto rowof = [&](int lb) -> int { return CALLS ? (lb < d.Bcall ? grp * d.Bcall + lb : B) : grp * Bt + lb; };
+    const int trow_sh = CALLS ? grp : 0;
     auto pair_live = [](int k) -> bool { return !(HALF && (k >> 1) % HT == HT - 1 && (k & 1)); };
     auto hc_of = [&](int c) -> int { return min(d.Hc, d.H - c * d.Hc); };
     const int cstride = d.res ? d.NB * BLKF : 0;   // floats between the chunk slots of the LDS images (0: one slot)
@@ -100,9 +103,9 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
 
     // ---- controllers (replicated in every workgroup of the group; deterministic => identical)
     for (int lb = tid; lb < Bt; lb += blockDim.x) {
-        const int b = grp * Bt + lb;
+        const int b = rowof(lb);
         const bool vb = b < B;
-        const TimeRow tb = trowT(t, T, cfg, shared ? 0 : (vb ? b : 0));
+        const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : (vb ? b : 0));
         float sg = 1.0f;
         int st = PHX_OK;
         if (T >= 2) {
@@ -122,7 +125,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
     for (int s = 0; s < d.TPW; ++s) {
         const int ttl = wv * d.TPW + s;
         if (ttl >= ntg) continue;
-        const int b = grp * Bt + ttl * 16 + li;
+        const int b = rowof(ttl * 16 + li);
         for (int bl = 0; bl < nbl; ++bl) {
             float xv[GW];
             const int g0 = (blk0 + bl) * 32 + gmap(lq, goff);
@@ -275,7 +278,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
         }
         __syncthreads();
         double v2[2] = {0.0, 0.0};
-        if (tid < Bt && (grp * Bt + tid) < B)
+        if (tid < Bt && rowof(tid) < B)
             for (int k = 0; k < nslots; ++k) v2[k] = (double)c.nrm[(tid >> 4) * 64 + k * 16 + (tid & 15)];
         if (!shared) {
             for (int k = 0; k < nslots; ++k) out[k] = sqrtf((float)(v2[k] / (double)N));
@@ -513,7 +516,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
                 liveF = true;
                 if (bl == 0 || sp) {
                     lb = ttl * 16 + li;
-                    b = grp * Bt + lb;
+                    b = rowof(lb);
                     kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
                     issue(ttl, sp ? bl : 0);   // before the hidden rows are waited for: the tile latency overlaps the poll
                     if (DO2) { gather(ttl, chL, tagIn); tm.mark(4); }
@@ -706,7 +709,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
             const int ttl = wv * d.TPW + s;
             if (ttl >= ntg) continue;
             const int lb = ttl * 16 + li;
-            const int b = grp * Bt + lb;
+            const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
             const bool rot = __builtin_amdgcn_readfirstlane(rotf[ttl]) != 0;
             const bool adv = !c.done[lb] && c.accept[lb];
@@ -715,7 +718,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
             const double t0 = c.rk_t0[lb], t1 = c.rk_t1[lb];
             const float dts = c.dtp[lb];
             const double sg = (double)c.sgn[lb];
-            const TimeRow tb = trowT(t, T, cfg, shared ? 0 : min(b, B - 1));
+            const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : min(b, B - 1));
             const bool outs = __any(adv && hi > lo);
             float y0A[GW], kA[7][GW], y0B[GW], kB[7][GW];
             auto request = [&](int bl, float(&y0v)[GW], float(&k)[7][GW]) {
@@ -837,8 +840,8 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
             // ---- controller (rk_common.py:150-220)
             if (tid < Bt && !c.done[tid]) {
                 const int lb = tid;
-                const int b = grp * Bt + lb;
-                const TimeRow tb = trowT(t, T, cfg, shared ? 0 : b);
+                const int b = rowof(lb);
+                const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : b);
                 const double sg = (double)c.sgn[lb];
                 const float ratio = nv[0];
                 const int acc = (ratio <= 1.0f) ? 1 : 0;
@@ -907,7 +910,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
         const int ttl = wv * d.TPW + s;
         if (ttl >= ntg) continue;
         const int lb = ttl * 16 + li;
-        const int b = grp * Bt + lb;
+        const int b = rowof(lb);
         if (b < B && T >= 2 && (c.st[lb] != PHX_OK || x.aborted))
             for (int bl = 0; bl < nbl; ++bl)
                 for (int jo = max(c.out_idx[lb], 1); jo < T; ++jo)
@@ -919,7 +922,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
     }
     if (gt == 0)
         for (int lb = tid; lb < Bt; lb += blockDim.x) {
-            const int b = grp * Bt + lb;
+            const int b = rowof(lb);
             if (b < B) {
                 status[b] = x.aborted ? (int)PHX_ERR_SYNC_TIMEOUT : c.st[lb];
                 nfe_out[b] = c.nfe[lb];

@@ -75,13 +75,17 @@ def forget_workspaces():
     _ws_last.clear()
 
 
-def _workspace(op, N, H, B, T, device, calls=1):
+def _workspace(op, N, H, B, T, device, calls=1, grids_method=None):
     # the size query re-plans the launch on the host: remembered per shape (and per diagnostic switch setting)
-    key = (op, N, H, B, T, calls) + _plan_env()
+    # grids_method: the calls have a time grid each (phx_odeint_calls_grids_workspace_bytes depends on the method)
+    key = (op, N, H, B, T, calls, grids_method) + _plan_env()
     nbytes = _ws_bytes.get(key)
     if nbytes is None:
         if calls > 1:
-            nbytes = _lib.load().phx_odeint_calls_workspace_bytes(N, H, B, T, calls)
+            if grids_method is not None:
+                nbytes = _lib.load().phx_odeint_calls_grids_workspace_bytes(N, H, B, T, calls, _lib.METHODS[grids_method])
+            else:
+                nbytes = _lib.load().phx_odeint_calls_workspace_bytes(N, H, B, T, calls)
             if nbytes == 0:
                 raise ValueError("a batch of %d calls x %d trajectories cannot be planned for N=%d, H=%d" %
                                  (calls, B // calls, N, H))
@@ -465,7 +469,8 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
     """y0 [B,N] f32, t64 [T] or [B,T] f64 (device) -> sol [T,B,N], status[B], nfe[B], nsteps[B].
     The engine writes NaN into the outputs a failed trajectory never reached (a backward solve launched before the
     status is read then stops at once).  calls > 1 (shared control): the rows are `calls` independent odeint calls
-    of B/calls rows each, every call with its own step controller (include/phoenix_hip.h, phx_solve_opts.calls).
+    of B/calls rows each, every call with its own step controller (include/phoenix_hip.h, phx_solve_opts.calls);
+    with t_per_sample, t64 is [calls, T], one grid per call.  ValueError where no batched plan exists.
     step_size > 0 (fixed-grid methods): options["step_size"], phx_odeint_stepped."""
     B, N = y0.shape
     step = _step_of(method, step_size)
@@ -480,7 +485,10 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
     if stats is None:      # not zero-filled: every solve kernel writes status / nfe / nsteps of every trajectory
         stats = torch.empty((3, B), dtype=torch.int32, device=y0.device)
     p.on_current_stream()
-    ws, nb = _workspace(_lib.OP_ODEINT, p.N, p.H, B, T, y0.device, calls)
+    if t_per_sample and control == _lib.CTRL_SHARED and (calls <= 1 or t64.shape[0] != calls):
+        raise ValueError("a shared step controller has one time grid; calls > 1 take t of shape [calls, T]")
+    ws, nb = _workspace(_lib.OP_ODEINT, p.N, p.H, B, T, y0.device, calls,
+                        method if calls > 1 and t_per_sample else None)
     pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), calls, step) + _plan_env()
 
     def call(keep):

@@ -242,29 +242,38 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
 def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     """K forward-only `odeint(func, y0s[k], t, ...)` calls in as few launches as the device has room for:
         y0s [K, *shape] (shape = [B,1,N] or [B,N]), t [T]  ->  [K, T, *shape]  (a view of the engine's [T, K*B, N]).
+    t [K, T]: one time grid per call, `odeint(func, y0s[k], t[k], ...)` -- the validation loop of train_insilico.py:77-106;
+    the grids may differ in start, span and direction, and dopri5 runs on the third-generation kernels.
     Every call keeps the reference's batch semantics -- ONE adaptive step size shared by its B trajectories, chosen
     from its own error norm -- so the result equals the K separate calls (the analysis loop of
     find_gene_influences.py:64-77 issues 2 per gene).  Falls back to K launches where the batched plan does not
     exist (shapes served by the VALU engine)."""
     K = y0s.shape[0]
+    grids = torch.is_tensor(t) and t.ndimension() == 2
+    if grids and t.shape[0] != K:
+        raise ValueError("odeint_calls: t must be [T] or [K, T] with K = %d calls, got %s" % (K, tuple(t.shape)))
+    t_of = (lambda k: t[k]) if grids else (lambda k: t)
     if K == 1:
         with torch.no_grad():     # forward-only by contract, like the batched launch below
-            return odeint(func, y0s[0], t, rtol, atol, method, options).unsqueeze(0)
+            return odeint(func, y0s[0], t_of(0), rtol, atol, method, options).unsqueeze(0)
     y0, t, rtol, atol, method, options = _check_inputs(func, y0s, t, rtol, atol, method, options)
-    params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t, options)
+    # (a grid per call is prepared as one shared grid: _prepare reads a 2-D t as one grid per TRAJECTORY)
+    params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t[0] if grids else t, options)
     if per_sample or control != _lib.CTRL_SHARED:
-        raise ValueError("odeint_calls: one shared time grid, batch_control='shared'")
+        raise ValueError("odeint_calls: one shared time grid per call, batch_control='shared'")
+    if grids:
+        t64 = t.detach().to(device=y0.device, dtype=t64.dtype).contiguous()
     if options.get("step_size"):      # the batched launch has no sub-step loop: the K calls themselves
         with torch.no_grad():
-            return torch.stack([odeint(func, y0s[k], t, rtol, atol, method, options) for k in range(K)])
+            return torch.stack([odeint(func, y0s[k], t_of(k), rtol, atol, method, options) for k in range(K)])
     engine.check_pending_status()
     p = engine.params_cached(*params)
     try:
-        sol, status, _, _ = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol, per_sample,
+        sol, status, _, _ = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol, grids,
                                                  t_is_f32, int(options.get("max_num_steps", 0)), calls=K)
     except ValueError:
         with torch.no_grad():
-            return torch.stack([odeint(func, y0s[k], t, rtol, atol, method, options) for k in range(K)])
+            return torch.stack([odeint(func, y0s[k], t_of(k), rtol, atol, method, options) for k in range(K)])
     engine.raise_for_status(status)
     return sol.reshape((sol.shape[0], K) + tuple(y0s.shape[1:])).transpose(0, 1)
 
