@@ -272,6 +272,23 @@ int phx_hill_rhs(const int *code, const int *off, const int *len, const float *c
 int phx_hill_simulate(const int *code, const int *off, const int *len, const float *consts, const float *x0,
                       const double *times, int T, double dt_max, float *out, int B, int N, void *stream);
 
+/* the scoring tail of the gene-influence scan (find_gene_influences.py:64-77) on the solver's
+ * own output.  sol [T, 2 * pairs * B, N] is the block phx_odeint wrote for 2 * pairs calls of B rows (opts->calls): call
+ * 2j is the unperturbed solve of pair j, call 2j + 1 the perturbed one; genes_host [pairs] (HOST) names the perturbed
+ * gene of every pair.  With
+ *     s[j, n]       = sum over tau = 1 .. T-1, b < B of | sol[tau, 2jB + b, n] - sol[tau, (2j+1)B + b, n] |
+ *     targets[j, n] = s[j, n] / ((T-1) B)                             mean |difference| of target gene n  (may be NULL)
+ *     scores[j]     = (sum over n != genes[j] of s[j, n]) / ((T-1) B (N-1))                        (:74-75)
+ * sol is read once (its tau = 0 slab not at all), every sum runs in an order fixed by the shape (no atomics: two calls
+ * on the same block agree bit for bit, with or without targets), column genes[j] is left out of the score by index and
+ * reported in targets as computed.  Non-finite inputs propagate (a NaN trajectory gives a NaN score).
+ * PHX_ERR_BAD_ARG before any device call: null sol / scores / genes_host, T < 2, pairs < 1 (or > 65535), B < 1, N < 2,
+ * a gene outside [0, N); PHX_ERR_WORKSPACE when workspace_bytes < phx_influence_workspace_bytes(T, pairs, B, N) (0 for a
+ * shape the call refuses): s lives there when targets is NULL. */
+size_t phx_influence_workspace_bytes(int T, int pairs, int B, int N);
+int phx_influence_scores(const float *sol, int T, int pairs, int B, int N, const int *genes_host, float *scores,
+                         float *targets, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

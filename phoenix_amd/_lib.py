@@ -34,7 +34,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped", "phx_odeint_backprop_backward",
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
-           "phx_debug_calls_grids_launches")
+           "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -114,6 +114,9 @@ def load():
     lib.phx_layout_params.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     lib.phx_debug_forward_kernel_m.argtypes = [C.c_int] * 6
     lib.phx_debug_solve_launches.argtypes = [C.c_int] * 7
+    lib.phx_influence_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.phx_influence_workspace_bytes.restype = C.c_size_t
+    lib.phx_influence_scores.argtypes = [vp] + [C.c_int] * 4 + [C.POINTER(C.c_int), vp, vp, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

@@ -7,12 +7,18 @@ shared adaptive step size per `odeint` call of the `[n_inputs, 1, N]` batch, 10 
 grid), but the two solves of `genes_per_launch` genes go to the engine together (`odeint_calls`: one batch group and
 one step controller per call, as many calls per launch as the device holds) and the scores stay on the device until
 the end (the reference calls `.item()` inside the loop).
+`fused=True` and `gene_influence_matrix` keep the scoring on the device as well: draws and perturbed copies are written
+straight into one initial-state buffer, the solver's output block is scored by one pass of phx_influence_scores
+(include/phoenix_hip.h) instead of six small launches per gene, and the per-target means that pass computes anyway are
+the gene -> gene influence matrix.
 `DataHandler.calculate_trajectory` (phoenix_amd/data.py) is the other caller of this row.
 """
 import numpy as np
 import torch
 
-from .odeint import odeint_calls
+from . import engine
+from .odeint import _calls_block, odeint_calls
+from .odenet import params_of
 
 
 def influence_score(unpert_out, pert_out, this_gene):
@@ -24,10 +30,15 @@ def influence_score(unpert_out, pert_out, this_gene):
 
 
 def gene_influence_scores(odenet, dim, method, n_random_inputs_per_gene=60, time_pts_to_project=None, device="cuda",
-                          genes=None, draws=None, genes_per_launch=8):
+                          genes=None, draws=None, genes_per_launch=8, fused=False):
     """Returns a float32 numpy array with one score per gene in `genes` (default: all `dim` genes, in order).
     `draws(gene) -> (this_init [n,1,dim], this_pert_col [n])` replaces the reference's two `torch.rand` calls
-    (find_gene_influences.py:69,71); by default they are drawn on `device` in the same order."""
+    (find_gene_influences.py:69,71); by default they are drawn on `device` in the same order.
+    `fused=True`: the same scan with the scoring in one kernel pass per launch (`gene_influence_matrix` without the
+    matrix); it differs from the default path in the order of the sums only."""
+    if fused:
+        return _fused_scan(odenet, dim, method, n_random_inputs_per_gene, time_pts_to_project, device, genes, draws,
+                           genes_per_launch, want_matrix=False)[0]
     if time_pts_to_project is None:
         time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # :65 (float64 grid)
     t = time_pts_to_project.to(device)
@@ -50,3 +61,46 @@ def gene_influence_scores(odenet, dim, method, n_random_inputs_per_gene=60, time
             for j, this_gene in enumerate(batch):
                 scores[k0 + j] = influence_score(out[2 * j], out[2 * j + 1], this_gene)
     return scores.cpu().numpy()
+
+
+def gene_influence_matrix(odenet, dim, method, n_random_inputs_per_gene=60, time_pts_to_project=None, device="cuda",
+                          genes=None, draws=None, genes_per_launch=8):
+    """The scan of `gene_influence_scores(fused=True)` with what it discards: returns (scores [G] float32 numpy,
+    matrix [G, dim] float32 tensor on `device`), G = len(genes).  matrix[i, n] = mean over the projected time points
+    after the first and over the random inputs of |unperturbed - perturbed| of target gene n when genes[i] is
+    perturbed; scores[i] is the mean of row i over n != genes[i] (find_gene_influences.py:74-75).  The diagonal entry
+    matrix[i, genes[i]] (the perturbed gene itself) is reported as computed and left out of the score only.  Same draws
+    in the same order as `gene_influence_scores`."""
+    return _fused_scan(odenet, dim, method, n_random_inputs_per_gene, time_pts_to_project, device, genes, draws,
+                       genes_per_launch, want_matrix=True)
+
+
+def _fused_scan(odenet, dim, method, n, time_pts_to_project, device, genes, draws, genes_per_launch, want_matrix):
+    engine._require_gpu(params_of(odenet)[0], "odenet")
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # :65 (float64 grid)
+    t = time_pts_to_project.to(device)
+    genes = list(range(dim)) if genes is None else [int(g) for g in genes]
+    k_max = max(1, min(int(genes_per_launch), len(genes)))
+    scores = torch.empty(len(genes), dtype=torch.float32, device=device)
+    matrix = torch.empty((len(genes), dim), dtype=torch.float32, device=device) if want_matrix else None
+    y0s = torch.empty((2 * k_max, n, 1, dim), dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for k0 in range(0, len(genes), k_max):
+            batch = genes[k0:k0 + k_max]
+            for j, this_gene in enumerate(batch):
+                init, pert = y0s[2 * j], y0s[2 * j + 1]
+                if draws is None:     # the two torch.rand calls of :69,71, in that order, into place
+                    torch.rand((n, 1, dim), out=init)
+                    init.sub_(0.5)
+                    col = torch.rand(n, device=device) - 0.5
+                else:
+                    this_init, col = draws(this_gene)
+                    init.copy_(this_init)
+                pert.copy_(init)
+                pert[:, 0, this_gene] = col
+            sol = _calls_block(odenet, y0s[:2 * len(batch)], t, method=method)      # [T, 2k*n, dim]
+            engine.influence_scores(sol, len(batch), n, batch, scores=scores[k0:k0 + len(batch)],
+                                    targets=matrix[k0:k0 + len(batch)] if want_matrix else None)
+            del sol       # one output block alive at a time
+    return scores.cpu().numpy(), matrix

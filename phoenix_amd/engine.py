@@ -575,3 +575,42 @@ def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_
 
     _solve_call(OP_BACKPROP, pkey, y_saved.device, call)
     return adj, grads, stats[0], stats[1], stats[2]
+
+
+OP_INFLUENCE = 5     # workspace-cache key of influence_scores (phx_influence_workspace_bytes sizes it)
+
+
+def influence_scores(sol, pairs, B, genes, want_targets=False, scores=None, targets=None):
+    """phx_influence_scores on the engine's output block sol [T, 2*pairs*B, N] (call 2j unperturbed, 2j+1 perturbed,
+    `genes[j]` the perturbed gene of pair j) -> (scores [pairs], targets [pairs, N] or None), both on the device.
+    `scores` / `targets`: contiguous float32 device tensors to write into instead of fresh ones (a row range of a
+    scan's result); passing `targets` implies want_targets."""
+    _require_gpu(sol, "sol")
+    if sol.dim() != 3 or not sol.is_contiguous() or sol.shape[1] != 2 * pairs * B:
+        raise ValueError("influence_scores: sol must be a contiguous [T, 2*pairs*B, N] block, got %s for pairs=%d, B=%d"
+                         % (tuple(sol.shape), pairs, B))
+    T, _, N = sol.shape
+    genes = [int(g) for g in genes]
+    if len(genes) != pairs:
+        raise ValueError("influence_scores: %d genes for %d pairs" % (len(genes), pairs))
+    if scores is None:
+        scores = torch.empty(pairs, dtype=torch.float32, device=sol.device)
+    if targets is None and want_targets:
+        targets = torch.empty((pairs, N), dtype=torch.float32, device=sol.device)
+    for name, x, numel in (("scores", scores, pairs), ("targets", targets, pairs * N)):
+        if x is not None:
+            _require_gpu(x, name)
+            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device:
+                raise ValueError("influence_scores: `%s` must be a contiguous tensor of %d elements on sol's device"
+                                 % (name, numel))
+    key = (OP_INFLUENCE, T, pairs, B, N)
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _ws_bytes[key] = _lib.load().phx_influence_workspace_bytes(T, pairs, B, N)
+    key = (sol.device.index, _stream_raw(sol.device.index), OP_INFLUENCE)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=sol.device)
+    _check_call(_lib.load().phx_influence_scores(_p(sol), T, pairs, B, N, (C.c_int * pairs)(*genes), _p(scores), _p(targets),
+                                                 _p(ws), nbytes, _stream_ptr()))
+    return scores, targets

@@ -239,6 +239,51 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
     return (out, nfe, nsteps) if return_stats else out
 
 
+def _calls_block(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
+    """the solves of `odeint_calls` as the engine's own output block: [T, K*B, N], call k in rows k*B .. (k+1)*B - 1 of
+    every output time (B = trajectories of one call).  One batched launch where the plan exists; else the K calls one by
+    one, copied into the same layout."""
+    K = y0s.shape[0]
+    grids = torch.is_tensor(t) and t.ndimension() == 2
+    if grids and t.shape[0] != K:
+        raise ValueError("odeint_calls: t must be [T] or [K, T] with K = %d calls, got %s" % (K, tuple(t.shape)))
+    t_of = (lambda k: t[k]) if grids else (lambda k: t)
+
+    def one_by_one():
+        block = None
+        with torch.no_grad():     # forward-only by contract, like the batched launch below
+            for k in range(K):
+                one = odeint(func, y0s[k], t_of(k), rtol, atol, method, options)
+                one = one.reshape(one.shape[0], -1, one.shape[-1])
+                if K == 1:
+                    return one
+                if block is None:
+                    block = torch.empty((one.shape[0], K) + tuple(one.shape[1:]), dtype=one.dtype, device=one.device)
+                block[:, k] = one
+        return block.reshape(block.shape[0], -1, block.shape[-1])
+
+    if K == 1:
+        return one_by_one()
+    y0, t, rtol, atol, method, options = _check_inputs(func, y0s, t, rtol, atol, method, options)
+    # (a grid per call is prepared as one shared grid: _prepare reads a 2-D t as one grid per TRAJECTORY)
+    params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t[0] if grids else t, options)
+    if per_sample or control != _lib.CTRL_SHARED:
+        raise ValueError("odeint_calls: one shared time grid per call, batch_control='shared'")
+    if grids:
+        t64 = t.detach().to(device=y0.device, dtype=t64.dtype).contiguous()
+    if options.get("step_size"):      # the batched launch has no sub-step loop: the K calls themselves
+        return one_by_one()
+    engine.check_pending_status()
+    p = engine.params_cached(*params)
+    try:
+        sol, status, _, _ = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol, grids,
+                                                 t_is_f32, int(options.get("max_num_steps", 0)), calls=K)
+    except ValueError:
+        return one_by_one()
+    engine.raise_for_status(status)
+    return sol
+
+
 def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     """K forward-only `odeint(func, y0s[k], t, ...)` calls in as few launches as the device has room for:
         y0s [K, *shape] (shape = [B,1,N] or [B,N]), t [T]  ->  [K, T, *shape]  (a view of the engine's [T, K*B, N]).
@@ -249,32 +294,7 @@ def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     find_gene_influences.py:64-77 issues 2 per gene).  Falls back to K launches where the batched plan does not
     exist (shapes served by the VALU engine)."""
     K = y0s.shape[0]
-    grids = torch.is_tensor(t) and t.ndimension() == 2
-    if grids and t.shape[0] != K:
-        raise ValueError("odeint_calls: t must be [T] or [K, T] with K = %d calls, got %s" % (K, tuple(t.shape)))
-    t_of = (lambda k: t[k]) if grids else (lambda k: t)
-    if K == 1:
-        with torch.no_grad():     # forward-only by contract, like the batched launch below
-            return odeint(func, y0s[0], t_of(0), rtol, atol, method, options).unsqueeze(0)
-    y0, t, rtol, atol, method, options = _check_inputs(func, y0s, t, rtol, atol, method, options)
-    # (a grid per call is prepared as one shared grid: _prepare reads a 2-D t as one grid per TRAJECTORY)
-    params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t[0] if grids else t, options)
-    if per_sample or control != _lib.CTRL_SHARED:
-        raise ValueError("odeint_calls: one shared time grid per call, batch_control='shared'")
-    if grids:
-        t64 = t.detach().to(device=y0.device, dtype=t64.dtype).contiguous()
-    if options.get("step_size"):      # the batched launch has no sub-step loop: the K calls themselves
-        with torch.no_grad():
-            return torch.stack([odeint(func, y0s[k], t_of(k), rtol, atol, method, options) for k in range(K)])
-    engine.check_pending_status()
-    p = engine.params_cached(*params)
-    try:
-        sol, status, _, _ = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol, grids,
-                                                 t_is_f32, int(options.get("max_num_steps", 0)), calls=K)
-    except ValueError:
-        with torch.no_grad():
-            return torch.stack([odeint(func, y0s[k], t_of(k), rtol, atol, method, options) for k in range(K)])
-    engine.raise_for_status(status)
+    sol = _calls_block(func, y0s, t, rtol, atol, method, options)
     return sol.reshape((sol.shape[0], K) + tuple(y0s.shape[1:])).transpose(0, 1)
 
 
