@@ -289,6 +289,30 @@ size_t phx_influence_workspace_bytes(int T, int pairs, int B, int N);
 int phx_influence_scores(const float *sol, int T, int pairs, int B, int N, const int *genes_host, float *scores,
                          float *targets, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The explainability matrices of a trained model, regulator i -> target j (the orientation of effects_mat and of the
+ * gene-influence matrix), from the engine layout as it is.  With s = y - 0.5 and r = relu(g):
+ *     S[i,j]   = sum_h Ws[h,i] WaT[h,j]                                          (state independent)
+ *     Q_b[i,j] = sum_h p[b,h] Wp[h,i] WaT[H+h,j]                                 p[b,:] = exp(Wp log1p(softsign(s_b)) + bp)
+ *     J_b[i,j] = d f_j / d y_i (y_b) = r_j ( a'(y_bi) S[i,j] + l'(y_bi) Q_b[i,j] - delta_ij )       (odenet.py:85-91)
+ *     a' = 1 / (1 + |s|)^2          l' = 1 / (1 + |s|) for s < 0,   1 / ((1 + s)(1 + 2 s)) for s >= 0
+ *     effects[i,j] = r_j ( S[i,j] + sum_h Wp[h,i] WaT[H+h,j] )                   (extract_model_matrix_PHOENIX.py:46-58;
+ *                                                                                 J with a' = l' = p = 1 and no delta)
+ * PHX_EFFECTS writes `effects` (y, ph and B are ignored), PHX_JAC_MEAN (1/B) sum_b J_b, PHX_JAC_MEAN_ABS (1/B) sum_b |J_b|
+ * over the states y [B, N].  ph [B, H] is the caller's product-branch hidden vector p[b,:] of those states; a' and l' are
+ * computed from y by the closed forms.  out [row1 - row0, N] (row-major) receives regulator rows row0 .. row1 - 1 only, so
+ * that a caller can walk a genome-scale matrix in chunks; delta belongs to global row i = column j whatever row0 is.
+ * One launch (phx_effects.hip): every 64 x 64 tile stays in MFMA accumulators over the hidden rows and over all B states,
+ * out is written exactly once and no N x N temporary is read or written.  Every entry is summed by one wave in an order
+ * fixed by (N, H, B, mode, i, j): no atomics, and its bits do not depend on the row range.  relu(g_j) = 0 gives exact
+ * zeros in column j; non-finite inputs propagate.  Of `p` the call reads Ws, Wp, WaT and g.
+ * PHX_ERR_BAD_ARG before any device call: null p / out / Ws / Wp / WaT / g, N < 2, H < 1, H > 256, row0 < 0, row1 > N,
+ * row0 >= row1, an unknown mode, a Jacobian mode with null y or ph or B < 1.  PHX_ERR_WORKSPACE when workspace_bytes <
+ * phx_effects_workspace_bytes(N, H, B, mode) (0 when none is needed or the shape is refused; today no shape needs any). */
+enum phx_effects_mode { PHX_EFFECTS = 0, PHX_JAC_MEAN = 1, PHX_JAC_MEAN_ABS = 2 };
+size_t phx_effects_workspace_bytes(int N, int H, int B, int mode);
+int phx_effects_matrix(const phx_params *p, int mode, const float *y, const float *ph, int B, int row0, int row1,
+                       float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

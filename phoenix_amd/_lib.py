@@ -34,11 +34,13 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped", "phx_odeint_backprop_backward",
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
-           "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores")
+           "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
+           "phx_effects_workspace_bytes", "phx_effects_matrix")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
 CTRL_SHARED, CTRL_PER_TRAJECTORY = 0, 1
+EFFECTS_MODES = {"effects": 0, "mean": 1, "mean_abs": 2}     # phx_effects_mode
 STATUS_TEXT = {
     1: "max_num_steps exceeded",
     2: "underflow in dt",
@@ -117,6 +119,9 @@ def load():
     lib.phx_influence_workspace_bytes.argtypes = [C.c_int] * 4
     lib.phx_influence_workspace_bytes.restype = C.c_size_t
     lib.phx_influence_scores.argtypes = [vp] + [C.c_int] * 4 + [C.POINTER(C.c_int), vp, vp, vp, C.c_size_t, vp]
+    lib.phx_effects_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.phx_effects_workspace_bytes.restype = C.c_size_t
+    lib.phx_effects_matrix.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 3 + [vp, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

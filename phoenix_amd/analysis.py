@@ -104,3 +104,40 @@ def _fused_scan(odenet, dim, method, n, time_pts_to_project, device, genes, draw
                                     targets=matrix[k0:k0 + len(batch)] if want_matrix else None)
             del sol       # one output block alive at a time
     return scores.cpu().numpy(), matrix
+
+
+def effects_matrix(odenet, rows=None, out=None):
+    """The reference's regulatory "effects matrix" (extract_model_matrix_PHOENIX.py:46-58) on the device:
+    effects[i, j] = relu(g_j) * (Ws^T Wa[:, :H]^T + Wp^T Wa[:, H:]^T)[i, j], regulator i -> target j, float32 [R, N].
+    `rows = (row0, row1)` computes regulator rows row0 .. row1 - 1 only (R = row1 - row0): at genome scale the matrix is
+    0.5 to 0.9 GB, and a caller may want it in pieces; `out` is written in place.  What the reference then dumps as CSV is
+    `.cpu().numpy()` of the result."""
+    tensors = params_of(odenet)
+    rows = engine.check_rows(rows, tensors[0].shape[1])
+    engine._require_gpu(tensors[0], "odenet")
+    with torch.no_grad():
+        return engine.effects_matrix(engine.params_cached(*tensors), "effects", rows=rows, out=out)
+
+
+def jacobian_matrix(odenet, y, reduce="mean_abs", rows=None, out=None):
+    """The Jacobian of the RHS (odenet.py:85-91) over a batch of expression states `y` ([B, N] or [B, 1, N], float32, on the
+    device), J_b[i, j] = d f_j / d y_i at y_b, averaged over the batch as it is (reduce="mean") or in absolute value
+    (reduce="mean_abs"): the state-dependent regulator -> target network that the influence scan samples by perturbation
+    and of which `effects_matrix` is the crude, state-free form.  float32 [R, N] on the device; `rows` and `out` as for
+    `effects_matrix`.  One kernel call: the [N, N] Jacobians of the states are never formed."""
+    if reduce not in ("mean", "mean_abs"):
+        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
+    tensors = params_of(odenet)
+    N = tensors[0].shape[1]
+    rows = engine.check_rows(rows, N)
+    engine._require_gpu(tensors[0], "odenet")
+    engine._require_gpu(y, "y")
+    if not ((y.dim() == 2 and y.shape[1] == N) or (y.dim() == 3 and y.shape[1:] == (1, N))) or y.shape[0] < 1:
+        raise ValueError("y must be [B, %d] or [B, 1, %d], got %s" % (N, N, tuple(y.shape)))
+    with torch.no_grad():
+        p = engine.params_cached(*tensors)
+        y2 = y.detach().reshape(y.shape[0], N).contiguous()
+        # the product branch's hidden vector of every state (odenet.py:87-88): a [B, N] x [N, H] contraction, plumbing
+        s = y2 - 0.5
+        ph = torch.exp(torch.addmm(p.bp, torch.log1p(s / (1 + s.abs())), p.Wp.t()))
+        return engine.effects_matrix(p, reduce, y=y2, ph=ph, rows=rows, out=out)

@@ -34,7 +34,7 @@ PROF_LIB = os.path.join(HERE, "libphoenix_prof.so")
 PROF_UNITS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_adj2.hip")
 # Units whose device assembly is also written to csrc/_obj/<unit>.s: every kernel that stores through buffer resources
 # (the store-data hazard is checked on these listings, tools/check_store_hazard.py)
-LISTINGS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_fwd3c.hip", "phx_adj3c.hip", "phx_bp.hip")
+LISTINGS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_fwd3c.hip", "phx_adj3c.hip", "phx_bp.hip", "phx_effects.hip")
 
 
 def sources():

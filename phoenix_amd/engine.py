@@ -614,3 +614,74 @@ def influence_scores(sol, pairs, B, genes, want_targets=False, scores=None, targ
     _check_call(_lib.load().phx_influence_scores(_p(sol), T, pairs, B, N, (C.c_int * pairs)(*genes), _p(scores), _p(targets),
                                                  _p(ws), nbytes, _stream_ptr()))
     return scores, targets
+
+
+OP_EFFECTS = 6       # workspace-cache key of effects_matrix (phx_effects_workspace_bytes sizes it)
+
+
+def check_rows(rows, N):
+    """(row0, row1) of a `rows` argument: None (all N rows) or a pair with 0 <= row0 < row1 <= N"""
+    if rows is None:
+        return 0, N
+    try:
+        row0, row1 = rows
+        row0, row1 = int(row0), int(row1)
+    except (TypeError, ValueError):
+        raise ValueError("rows must be None or (row0, row1), got %r" % (rows,))
+    if not 0 <= row0 < row1 <= N:
+        raise ValueError("rows must satisfy 0 <= row0 < row1 <= %d, got %r" % (N, rows))
+    return row0, row1
+
+
+def _require_f32(x, name):
+    """a device buffer the kernel reads or writes as float: any other dtype (an integer one passes _require_gpu) would be
+    read or written past its end"""
+    _require_gpu(x, name)
+    if x.dtype != torch.float32:
+        raise TypeError("phoenix_amd: `%s` must be float32 (got %s)" % (name, x.dtype))
+
+
+def effects_matrix(params, mode, y=None, ph=None, rows=None, out=None):
+    """phx_effects_matrix on laid-out parameters (`Params`): rows [row0, row1) of the regulator -> target matrix of `mode`
+    ("effects": extract_model_matrix_PHOENIX.py:46-58; "mean" / "mean_abs": the RHS Jacobian averaged over the states
+    y [B, N] as it is / in absolute value, with ph [B, H] the product-branch hidden vector of those states) -> float32
+    [row1 - row0, N] on the device.  `rows`: None (all N) or (row0, row1).  `out`: a contiguous float32 device tensor of
+    that shape to write into instead of a fresh one."""
+    if mode not in _lib.EFFECTS_MODES:
+        raise ValueError("effects_matrix: mode must be one of %s, got %r" % (sorted(_lib.EFFECTS_MODES), mode))
+    N, H = params.N, params.H
+    row0, row1 = check_rows(rows, N)
+    B = 1
+    if mode != "effects":
+        if y is None or ph is None:
+            raise ValueError("effects_matrix: mode %r needs the states `y` [B, N] and `ph` [B, H]" % mode)
+        _require_f32(y, "y")
+        _require_f32(ph, "ph")
+        B = y.shape[0] if y.dim() == 2 else 0
+        if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
+                y.device != params.device or ph.device != params.device:
+            raise ValueError("effects_matrix: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
+                             "parameters' device, got %s and %s" % (N, H, tuple(y.shape), tuple(ph.shape)))
+    else:
+        y = ph = None
+    if out is None:
+        out = torch.empty((row1 - row0, N), dtype=torch.float32, device=params.device)
+    else:
+        _require_f32(out, "out")
+        if tuple(out.shape) != (row1 - row0, N) or not out.is_contiguous() or out.device != params.device:
+            raise ValueError("effects_matrix: `out` must be a contiguous [%d, %d] tensor on the parameters' device"
+                             % (row1 - row0, N))
+    key = (OP_EFFECTS, N, H, B, mode)
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _ws_bytes[key] = _lib.load().phx_effects_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode])
+    ws = None
+    if nbytes:
+        key = (params.device.index, _stream_raw(params.device.index), OP_EFFECTS)
+        ws = _ws_cache.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=params.device)
+    p = params.on_current_stream()
+    _check_call(_lib.load().phx_effects_matrix(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, row0, row1, _p(out),
+                                               _p(ws), nbytes, _stream_ptr()))
+    return out
