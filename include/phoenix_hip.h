@@ -313,6 +313,37 @@ size_t phx_effects_workspace_bytes(int N, int H, int B, int mode);
 int phx_effects_matrix(const phx_params *p, int mode, const float *y, const float *ph, int B, int row0, int row1,
                        float *out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The strongest regulator -> target edges of those matrices without the matrices: M = what phx_effects_matrix writes for
+ * (mode, y, ph, B), entry M[i,j] eligible when it is finite and non-zero, i != j (or PHX_EDGES_DIAGONAL is set) and, with
+ * PHX_EDGES_ORIENT, |M[i,j]| > |M[j,i]| strictly (make_mask of extract_model_matrix_PHOENIX.py:29-37: of every gene pair the
+ * stronger direction only; the diagonal is then never eligible, an equally strong pair loses both directions, a NaN partner
+ * loses the comparison).  Magnitudes are compared as m = bits & 0x7fffffff.  phx_edges.hip runs the tile engine of
+ * phx_effects_matrix with a selection epilogue in place of the store (with ORIENT a workgroup forms tiles (I, J) and (J, I)
+ * and transposes one through LDS): every reported value has the bits phx_effects_matrix writes for that entry, and no
+ * N x N buffer is read or written.  A selection is a sequence of passes, each ONE launch that recomputes every tile (in the
+ * Jacobian modes each pass therefore repeats the loop over the B states); the caller reads the small results between them:
+ *   PHX_EDGES_COUNT  workspace: unsigned hist[4096] (zeroed by the call, then summed with integer atomics: exact and
+ *                    independent of arrival order).  level 0: hist[m >> 19] over all eligible entries; level 1:
+ *                    hist[(m >> 7) & 4095] over the eligible entries with (m >> 19) == prefix.  From the top, the bin where
+ *                    the running sum reaches K bounds the K strongest edges; the sum down to a bin sizes the next pass.
+ *   PHX_EDGES_EMIT   every eligible entry with |M[i,j]| >= tau is appended: keys[n] = (0x7fffffff - m) << 32 | (i N + j),
+ *                    values[n] = M[i,j], in no particular order; workspace: unsigned count at byte 16384 (zeroed by the
+ *                    call) = how many entries qualified.  Entries beyond `capacity` are counted and not written, so
+ *                    count > capacity tells a too-small buffer and by how much.  Sorting the keys ascending orders the
+ *                    edges by magnitude descending, then i, then j: the sorted list is bitwise reproducible.
+ * keys, values and capacity are ignored by COUNT; level and prefix by EMIT, tau by COUNT.  Nothing allocates or synchronises.
+ * PHX_ERR_BAD_ARG before any device call: null p / Ws / Wp / WaT / g, N < 2, N > 65535 (i N + j is 32 bits of the key),
+ * H < 1, H > 256, an unknown mode, a Jacobian mode with null y or ph or B < 1, unknown flags, an unknown pass, a level
+ * other than 0 and 1, a level-1 prefix >= 0xff0 (not finite), EMIT with null keys or values, capacity < 1, or tau not
+ * positive and finite.  PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_effects_edges_workspace_bytes(N, H, B, mode) (16448 for a served shape, 0 for one the call refuses). */
+enum phx_edges_flags { PHX_EDGES_ORIENT = 1, PHX_EDGES_DIAGONAL = 2 };
+enum phx_edges_pass { PHX_EDGES_COUNT = 0, PHX_EDGES_EMIT = 1 };
+size_t phx_effects_edges_workspace_bytes(int N, int H, int B, int mode);
+int phx_effects_edges(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, int pass, int level,
+                      unsigned prefix, float tau, long long *keys, float *values, unsigned capacity, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

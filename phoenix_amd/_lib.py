@@ -35,12 +35,15 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
            "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
-           "phx_effects_workspace_bytes", "phx_effects_matrix")
+           "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
 CTRL_SHARED, CTRL_PER_TRAJECTORY = 0, 1
 EFFECTS_MODES = {"effects": 0, "mean": 1, "mean_abs": 2}     # phx_effects_mode
+EDGES_ORIENT, EDGES_DIAGONAL = 1, 2                          # phx_edges_flags
+EDGES_COUNT, EDGES_EMIT = 0, 1                               # phx_edges_pass
+EDGES_BINS = 4096                                            # workspace: uint32 hist[EDGES_BINS], then uint32 count
 STATUS_TEXT = {
     1: "max_num_steps exceeded",
     2: "underflow in dt",
@@ -122,6 +125,10 @@ def load():
     lib.phx_effects_workspace_bytes.argtypes = [C.c_int] * 4
     lib.phx_effects_workspace_bytes.restype = C.c_size_t
     lib.phx_effects_matrix.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 3 + [vp, vp, C.c_size_t, vp]
+    lib.phx_effects_edges_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.phx_effects_edges_workspace_bytes.restype = C.c_size_t
+    lib.phx_effects_edges.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 4 + \
+        [C.c_uint, C.c_float, vp, vp, C.c_uint, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

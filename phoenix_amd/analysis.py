@@ -13,6 +13,8 @@ straight into one initial-state buffer, the solver's output block is scored by o
 the gene -> gene influence matrix.
 `DataHandler.calculate_trajectory` (phoenix_amd/data.py) is the other caller of this row.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -131,13 +133,46 @@ def jacobian_matrix(odenet, y, reduce="mean_abs", rows=None, out=None):
     N = tensors[0].shape[1]
     rows = engine.check_rows(rows, N)
     engine._require_gpu(tensors[0], "odenet")
+    with torch.no_grad():
+        p = engine.params_cached(*tensors)
+        y2, ph = _states(p, y)
+        return engine.effects_matrix(p, reduce, y=y2, ph=ph, rows=rows, out=out)
+
+
+def _states(p, y):
+    """(y [B, N] contiguous, ph [B, H]) of states `y` ([B, N] or [B, 1, N]) for the Jacobian modes of the engine"""
+    N = p.N
     engine._require_gpu(y, "y")
     if not ((y.dim() == 2 and y.shape[1] == N) or (y.dim() == 3 and y.shape[1:] == (1, N))) or y.shape[0] < 1:
         raise ValueError("y must be [B, %d] or [B, 1, %d], got %s" % (N, N, tuple(y.shape)))
+    y2 = y.detach().reshape(y.shape[0], N).contiguous()
+    # the product branch's hidden vector of every state (odenet.py:87-88): a [B, N] x [N, H] contraction, plumbing
+    s = y2 - 0.5
+    return y2, torch.exp(torch.addmm(p.bp, torch.log1p(s / (1 + s.abs())), p.Wp.t()))
+
+
+Edges = collections.namedtuple("Edges", ("regulator", "target", "value"))
+
+
+def effects_edges(odenet, top=None, threshold=None, orient=False, diagonal=False, y=None, reduce="mean_abs", max_edges=None):
+    """The strongest regulator -> target edges of `effects_matrix(odenet)` (y=None) or of `jacobian_matrix(odenet, y,
+    reduce)` without the [N, N] matrix: Edges(regulator int64 [E], target int64 [E], value float32 [E]) on the device,
+    sorted by |value| descending, then regulator, then target; every value has the bits of the matrix entry.
+    An entry is eligible when it is finite and non-zero and off the diagonal (`diagonal=True` admits the diagonal);
+    `orient=True` keeps of every gene pair the strictly stronger direction only, the reference's `make_mask`
+    (extract_model_matrix_PHOENIX.py:29-37): the diagonal and both directions of an equally strong pair are dropped.
+    Exactly one of `threshold` (all eligible entries with |value| >= threshold) and `top` (the K strongest; ties at the
+    cut go to the smaller regulator, then target; fewer than K eligible: all of them) selects.
+    The kernel recomputes the tiles in every pass (count, at most one refinement, emit), so with `y` each pass repeats the
+    loop over the states; `threshold` with `max_edges` is one pass into a list of that capacity and raises RuntimeError,
+    naming the true count, when more entries qualify."""
+    if y is not None and reduce not in ("mean", "mean_abs"):
+        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
+    engine.check_edges_selection(top, threshold, max_edges)
+    tensors = params_of(odenet)
+    engine._require_gpu(tensors[0], "odenet")
     with torch.no_grad():
         p = engine.params_cached(*tensors)
-        y2 = y.detach().reshape(y.shape[0], N).contiguous()
-        # the product branch's hidden vector of every state (odenet.py:87-88): a [B, N] x [N, H] contraction, plumbing
-        s = y2 - 0.5
-        ph = torch.exp(torch.addmm(p.bp, torch.log1p(s / (1 + s.abs())), p.Wp.t()))
-        return engine.effects_matrix(p, reduce, y=y2, ph=ph, rows=rows, out=out)
+        y2, ph = (None, None) if y is None else _states(p, y)
+        return Edges(*engine.effects_edges(p, "effects" if y is None else reduce, y=y2, ph=ph, top=top, threshold=threshold,
+                                           orient=orient, diagonal=diagonal, max_edges=max_edges))

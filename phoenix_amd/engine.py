@@ -5,6 +5,7 @@ path happens in libphoenix_hip.so."""
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -685,3 +686,150 @@ def effects_matrix(params, mode, y=None, ph=None, rows=None, out=None):
     _check_call(_lib.load().phx_effects_matrix(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, row0, row1, _p(out),
                                                _p(ws), nbytes, _stream_ptr()))
     return out
+
+
+OP_EDGES = 7         # workspace-cache key of effects_edges (phx_effects_edges_workspace_bytes sizes it)
+EDGES_REFINE_MIN = 1 << 20    # a cut bin with more entries than max(4 K, this) is refined on the next 12 bits
+
+
+def _is_int(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def _f32_bits(x):
+    return int(np.float32(x).view(np.uint32))
+
+
+def _edges_tau(threshold):
+    """the smallest float32 that is >= threshold (|M| >= threshold for a float32 M means |M| >= that), or None when
+    there is none"""
+    t = np.float32(threshold)
+    if float(t) < threshold:
+        t = np.nextafter(t, np.float32(np.inf))
+    return float(t) if np.isfinite(t) else None
+
+
+def check_edges_selection(top, threshold, max_edges):
+    """the ValueErrors of the selection arguments of `effects_edges`"""
+    if (top is None) == (threshold is None):
+        raise ValueError("effects_edges: exactly one of `top` and `threshold` must be given")
+    if top is not None and (not _is_int(top) or top < 1):
+        raise ValueError("effects_edges: top must be an integer >= 1, got %r" % (top,))
+    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and
+                                      not isinstance(threshold, bool) and threshold > 0 and np.isfinite(threshold)):
+        raise ValueError("effects_edges: threshold must be positive and finite, got %r" % (threshold,))
+    if max_edges is not None:
+        if threshold is None:
+            raise ValueError("effects_edges: max_edges applies to `threshold` only")
+        if not _is_int(max_edges) or not 1 <= max_edges < 2 ** 32:
+            raise ValueError("effects_edges: max_edges must be an integer in [1, 2^32), got %r" % (max_edges,))
+
+
+def effects_edges(params, mode, y=None, ph=None, top=None, threshold=None, orient=False, diagonal=False, max_edges=None,
+                  refine_above=None):
+    """phx_effects_edges on laid-out parameters (`Params`): the eligible entries (include/phoenix_hip.h) of the matrix
+    `effects_matrix(params, mode, y, ph)` would return -- all with |M[i,j]| >= threshold, or the `top` strongest (ties at
+    the cut to the smaller i, then j) -- as (regulator int64 [E], target int64 [E], value float32 [E]) on the device,
+    sorted by magnitude descending, then i, then j.  The matrix is not formed: a COUNT pass (a histogram of the magnitude
+    bits, read by the host) sizes the candidate list, at most one more refines the cut bin, an EMIT pass fills the list,
+    and a sort of the candidates' 64-bit keys orders it.  `max_edges` (threshold only): no COUNT pass, one EMIT pass into
+    a list of that capacity; RuntimeError with the true count when more entries qualify.  `refine_above`: the cap on the
+    entries of the cut bin (default max(4 top, 2^20)): a fuller bin is refined once on its next 12 bits, and `top` raises
+    RuntimeError when the refined cut bin is still fuller."""
+    if mode not in _lib.EFFECTS_MODES:
+        raise ValueError("effects_edges: mode must be one of %s, got %r" % (sorted(_lib.EFFECTS_MODES), mode))
+    check_edges_selection(top, threshold, max_edges)
+    N, H = params.N, params.H
+    if H > 256 or N > 65535:
+        raise ValueError("effects_edges: H <= 256 and N <= 65535 are served, got N=%d, H=%d" % (N, H))
+    B = 1
+    if mode != "effects":
+        if y is None or ph is None:
+            raise ValueError("effects_edges: mode %r needs the states `y` [B, N] and `ph` [B, H]" % mode)
+        _require_f32(y, "y")
+        _require_f32(ph, "ph")
+        B = y.shape[0] if y.dim() == 2 else 0
+        if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
+                y.device != params.device or ph.device != params.device:
+            raise ValueError("effects_edges: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
+                             "parameters' device, got %s and %s" % (N, H, tuple(y.shape), tuple(ph.shape)))
+    else:
+        y = ph = None
+    dev = params.device
+    lib = _lib.load()
+    nbytes = lib.phx_effects_edges_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode])
+    key = (dev.index, _stream_raw(dev.index), OP_EDGES)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _ws_cache[key] = torch.empty(int(nbytes) // 4 + 16, dtype=torch.int32, device=dev)
+    p = params.on_current_stream()
+    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
+
+    def run(pass_, level=0, prefix=0, tau=0.0, keys=None, values=None):
+        _check_call(lib.phx_effects_edges(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, pass_, level,
+                                          prefix, tau, _p(keys), _p(values), 0 if keys is None else keys.numel(), _p(ws),
+                                          nbytes, _stream_ptr()))
+
+    def histogram(level, prefix=0):
+        run(_lib.EDGES_COUNT, level, prefix)
+        return ws[:_lib.EDGES_BINS].cpu().numpy().astype(np.int64) & 0xFFFFFFFF    # the one small host read of the pass
+
+    def empty():
+        z = torch.empty(0, dtype=torch.int64, device=dev)
+        return z, z.clone(), torch.empty(0, dtype=torch.float32, device=dev)
+
+    if top is not None:
+        K = int(top)
+        cap = max(4 * K, EDGES_REFINE_MIN) if refine_above is None else int(refine_above)
+        h = histogram(0)
+        above = np.cumsum(h[::-1])[::-1]                    # above[b] = eligible entries in bins b ..
+        if above[0] == 0:
+            return empty()
+        lo, cand = 1, int(above[0])                         # fewer than K eligible: all of them
+        if above[0] > K:
+            c = int(np.nonzero(above >= K)[0][-1])          # the cut bin
+            lo, cand = c << 19, int(above[c])
+            if h[c] > cap:
+                h2 = histogram(1, c)
+                assert int(h2.sum()) == int(h[c])
+                above2 = np.cumsum(h2[::-1])[::-1] + (above[c] - h[c])
+                c2 = int(np.nonzero(above2 >= K)[0][-1])
+                if h2[c2] > cap:
+                    raise RuntimeError("effects_edges: %d entries share the magnitude at the cut of top=%d (to 24 bits); "
+                                       "the candidate list is capped at %d" % (int(h2[c2]), K, cap))
+                lo, cand = (c << 19) | (c2 << 7), int(above2[c2])
+        tau = float(np.uint32(max(lo, 1)).view(np.float32))
+        capacity = cand
+    else:
+        K = None
+        tau = _edges_tau(float(threshold))
+        if tau is None:
+            return empty()
+        if max_edges is not None:
+            capacity = int(max_edges)
+        else:
+            tb = _f32_bits(tau)
+            c = tb >> 19
+            h = histogram(0)
+            capacity = int(h[c:].sum())
+            if h[c] > (EDGES_REFINE_MIN if refine_above is None else int(refine_above)):    # the bin of tau itself is an upper bound: tighten it
+                h2 = histogram(1, c)
+                capacity = int(h[c + 1:].sum() + h2[(tb >> 7) & (_lib.EDGES_BINS - 1):].sum())
+            if capacity == 0:
+                return empty()
+        if capacity >= 2 ** 32:
+            raise ValueError("effects_edges: %d candidate edges do not fit one list" % capacity)
+    keys = torch.empty(capacity, dtype=torch.int64, device=dev)
+    values = torch.empty(capacity, dtype=torch.float32, device=dev)
+    run(_lib.EDGES_EMIT, tau=tau, keys=keys, values=values)
+    n = int(ws[_lib.EDGES_BINS].item()) & 0xFFFFFFFF
+    if n > capacity:
+        if max_edges is not None:
+            raise RuntimeError("effects_edges: %d edges qualify, max_edges=%d holds fewer; nothing is returned"
+                               % (n, capacity))
+        raise RuntimeError("effects_edges: the emit pass found %d entries where the count pass found %d" % (n, capacity))
+    keys, order = torch.sort(keys[:n])
+    if K is not None:
+        keys, order = keys[:K], order[:K]
+    flat = keys & 0xFFFFFFFF
+    return torch.div(flat, N, rounding_mode="floor"), flat % N, values[order]
