@@ -344,6 +344,37 @@ int phx_effects_edges(const phx_params *p, int mode, const float *y, const float
                       unsigned prefix, float tau, long long *keys, float *values, unsigned capacity, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Scoring those matrices against a known network (the network-recovery AUROC of the PHOENIX paper; the reference's only
+ * scorer, COMPUTE_GRN_AUROC of GRN_rnaode.py:10-22, walks a Python list of all N^2 edges) without the matrices: the two
+ * device passes of phx_netscore.hip, each ONE launch of the tile engine of phx_effects_matrix that recomputes every tile.
+ * M = what phx_effects_matrix writes for (mode, y, ph, B).  The SCORED matrix is M itself or, with PHX_EDGES_ORIENT,
+ * make_mask of M (extract_model_matrix_PHOENIX.py:29-37): an entry keeps its value only when |M[i,j]| > |M[j,i]| as floats,
+ * strictly (a NaN on either side fails the comparison); every other entry and the whole diagonal are +0.  The score of an
+ * entry is its magnitude bits m = bits & 0x7fffffff.  Scored entries: all i != j inside N, and the diagonal too with
+ * PHX_EDGES_DIAGONAL (RANK only; GATHER answers whatever it is asked).  Zeros are scored like every other value.
+ *   phx_effects_gather       values[n] = the scored matrix's entry keys[n] = i N + j, n < n_keys (duplicates allowed), with
+ *                            the bits of that entry.  The keys are grouped by 64 x 64 tile: with T = ceil(N / 64) the keys of
+ *                            tile t = (i / 64) T + j / 64 are keys[tile_offsets[t] .. tile_offsets[t + 1]), tile_offsets
+ *                            [T T + 1] ascending from 0 to n_keys (offsets are clamped to n_keys; a key that does not lie in
+ *                            the tile of its segment receives a NaN).  Workgroups whose segments are empty form no tile.
+ *   phx_effects_rank_counts  u [m] = distinct magnitude bits, ascending (the caller's positives).  counts [2 m + 1] (zeroed by
+ *                            the call): every scored entry of magnitude x is counted once, in counts[2 lb + 1] when
+ *                            u[lb] == x and in counts[2 lb] otherwise, lb = #{k : u[k] < x}; so counts[2 k + 1] entries tie
+ *                            with u[k] and counts[2 k] lie strictly between u[k - 1] and u[k].  A non-finite scored entry is
+ *                            counted in the unsigned at byte 0 of the workspace (zeroed by the call) and in no bucket.
+ *                            Integer atomics only: the counts are exact and independent of arrival order; the two lowest
+ *                            and two highest buckets leave each workgroup as one atomic.
+ * Nothing allocates or synchronises.  PHX_ERR_BAD_ARG before any device call: null p / Ws / Wp / WaT / g, N < 2, N > 65535
+ * (a key is 32 bits and a count fits 32), H < 1, H > 256, an unknown mode, a Jacobian mode with null y or ph or B < 1,
+ * unknown flags; gather: null keys / tile_offsets / values, n_keys < 1; rank: null u / counts, m < 1, m > 2^31 - 1.
+ * PHX_ERR_WORKSPACE (rank) when workspace is null or workspace_bytes < phx_effects_rank_workspace_bytes(N, H, B, mode) (64
+ * for a served shape, 0 for one the calls refuse). */
+size_t phx_effects_rank_workspace_bytes(int N, int H, int B, int mode);
+int phx_effects_gather(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, const unsigned *keys,
+                       const unsigned *tile_offsets, unsigned n_keys, float *values, void *stream);
+int phx_effects_rank_counts(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, const unsigned *u,
+                            unsigned m, unsigned *counts, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

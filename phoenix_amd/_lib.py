@@ -35,7 +35,8 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
            "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
-           "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges")
+           "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges",
+           "phx_effects_rank_workspace_bytes", "phx_effects_gather", "phx_effects_rank_counts")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -129,6 +130,11 @@ def load():
     lib.phx_effects_edges_workspace_bytes.restype = C.c_size_t
     lib.phx_effects_edges.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 4 + \
         [C.c_uint, C.c_float, vp, vp, C.c_uint, vp, C.c_size_t, vp]
+    lib.phx_effects_rank_workspace_bytes.argtypes = [C.c_int] * 4
+    lib.phx_effects_rank_workspace_bytes.restype = C.c_size_t
+    lib.phx_effects_gather.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, C.c_uint, vp, vp]
+    lib.phx_effects_rank_counts.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_uint, vp, vp,
+                                            C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

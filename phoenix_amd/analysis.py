@@ -176,3 +176,81 @@ def effects_edges(odenet, top=None, threshold=None, orient=False, diagonal=False
         y2, ph = (None, None) if y is None else _states(p, y)
         return Edges(*engine.effects_edges(p, "effects" if y is None else reduce, y=y2, ph=ph, top=top, threshold=threshold,
                                            orient=orient, diagonal=diagonal, max_edges=max_edges))
+
+
+def read_network(fp, gene_names):
+    """Host parser of the reference's edge files (breast_cancer_data/clean_data/validation_network.csv, the simulator's
+    edge_properties_G*.csv): a header row, then the regulator's and the target's gene name in the first two columns, quoted
+    or not; further columns are ignored.  `gene_names`: the names of the model's genes in row order, a list or the path of
+    a one-column names file with a header row (desmedt_gene_names_*.csv, gene_names_*.csv).  Returns (regulator, target) as
+    int64 numpy arrays: rows that name an unknown gene and duplicates are dropped, the order is ascending (regulator,
+    target)."""
+    import csv
+    if isinstance(gene_names, (str, bytes)) or hasattr(gene_names, "__fspath__"):
+        with open(gene_names, newline="") as f:
+            gene_names = [row[0] for row in list(csv.reader(f))[1:] if row]
+    index = {}
+    for k, name in enumerate(gene_names):
+        index.setdefault(str(name), k)
+    pairs = set()
+    with open(fp, newline="") as f:
+        rows = csv.reader(f)
+        next(rows, None)                       # the header
+        for row in rows:
+            if len(row) < 2:
+                continue
+            i, j = index.get(row[0]), index.get(row[1])
+            if i is not None and j is not None:
+                pairs.add((i, j))
+    pairs = np.array(sorted(pairs), dtype=np.int64).reshape(-1, 2)
+    return pairs[:, 0].copy(), pairs[:, 1].copy()
+
+
+NetworkScore = collections.namedtuple("NetworkScore", ("auroc", "average_precision", "n_positive", "n_negative", "threshold",
+                                                       "tp", "fp"))
+
+
+def _network_call(name, odenet, regulator, target, y, reduce):
+    """the checks `effects_at` and `network_score` share, in the order host errors first: (Params, mode, y2, ph, regulator,
+    target) with the index tensors on the model's device"""
+    if y is not None and reduce not in ("mean", "mean_abs"):
+        raise ValueError('%s: reduce must be "mean" or "mean_abs", got %r' % (name, reduce))
+    tensors = params_of(odenet)
+    regulator, target = engine.check_network_indices(name, regulator, target, tensors[0].shape[1])
+    engine._require_gpu(tensors[0], "odenet")
+    p = engine.params_cached(*tensors)
+    y2, ph = (None, None) if y is None else _states(p, y)
+    return p, "effects" if y is None else reduce, y2, ph, regulator.to(p.device), target.to(p.device)
+
+
+def effects_at(odenet, regulator, target, orient=False, y=None, reduce="mean_abs"):
+    """The entries (regulator[e], target[e]) of `effects_matrix(odenet)` (y=None) or of `jacobian_matrix(odenet, y, reduce)`
+    without the [N, N] matrix: float32 [E] on the device, in the caller's order (duplicates allowed), every value with the
+    bits of the matrix entry.  `orient=True` reads the reference's `make_mask` form of the matrix
+    (extract_model_matrix_PHOENIX.py:29-37) instead: the weaker or equally strong direction of a gene pair and the diagonal
+    are +0.  Only the 64 x 64 tiles that hold a listed entry are computed."""
+    with torch.no_grad():
+        p, mode, y2, ph, r, t = _network_call("effects_at", odenet, regulator, target, y, reduce)
+        return engine.effects_gather(p, mode, r, t, y=y2, ph=ph, orient=orient)
+
+
+def network_score(odenet, regulator, target, orient=False, diagonal=False, y=None, reduce="mean_abs"):
+    """How well the model's network recovers a known one (the network-recovery AUROC of the PHOENIX paper; the reference's
+    COMPUTE_GRN_AUROC, GRN_rnaode.py:10-22, without its list of all N^2 edges): every entry of `effects_matrix(odenet)`
+    (y=None) or `jacobian_matrix(odenet, y, reduce)` is scored by its magnitude, the pairs (regulator[e], target[e]) -- e.g.
+    from `read_network` -- are the positives (duplicates count once), every other scored entry is a negative.  Scored are
+    all off-diagonal entries (get_link_list, GRN_rnaode.py:119: "Auto-regulations do not appear"); `diagonal=True` adds the diagonal, and
+    positives on an excluded diagonal are dropped.  `orient=True` scores the `make_mask` form of the matrix (of every gene
+    pair only the strictly stronger direction keeps its magnitude, everything else scores 0).  Zeros are scored like any
+    other value: ties.
+    Returns NetworkScore(auroc, average_precision, n_positive, n_negative, threshold, tp, fp): `threshold` float32 [m], the
+    distinct magnitudes of the positives, descending; `tp`, `fp` int64 [m] on the device, the positives and negatives with
+    magnitude >= threshold[k] (the ROC and precision-recall points at the thresholds where they bend); auroc and
+    average_precision are Python floats with the tie handling of sklearn's roc_auc_score and average_precision_score,
+    computed from exact integer counts.  The matrix is never formed: one kernel pass reads the positives' values, a second
+    counts every entry against them.
+    ValueError: index arrays of unequal length or out of range, a bad `reduce`, labels of one class only ("Only one class
+    present"), or a scored entry that is not finite (the count is named)."""
+    with torch.no_grad():
+        p, mode, y2, ph, r, t = _network_call("network_score", odenet, regulator, target, y, reduce)
+        return NetworkScore(*engine.network_score(p, mode, r, t, y=y2, ph=ph, orient=orient, diagonal=diagonal))

@@ -833,3 +833,146 @@ def effects_edges(params, mode, y=None, ph=None, top=None, threshold=None, orien
         keys, order = keys[:K], order[:K]
     flat = keys & 0xFFFFFFFF
     return torch.div(flat, N, rounding_mode="floor"), flat % N, values[order]
+
+
+OP_NETSCORE = 8      # workspace-cache key of network_score (phx_effects_rank_workspace_bytes sizes it)
+NETSCORE_TILE = 64   # the tile by which phx_effects_gather wants its keys grouped
+
+
+def _netscore_states(name, params, mode, y, ph):
+    """(y, ph, B) of the scoring calls, checked as `effects_edges` checks them"""
+    if mode not in _lib.EFFECTS_MODES:
+        raise ValueError("%s: mode must be one of %s, got %r" % (name, sorted(_lib.EFFECTS_MODES), mode))
+    N, H = params.N, params.H
+    if H > 256 or N > 65535:
+        raise ValueError("%s: H <= 256 and N <= 65535 are served, got N=%d, H=%d" % (name, N, H))
+    if mode == "effects":
+        return None, None, 1
+    if y is None or ph is None:
+        raise ValueError("%s: mode %r needs the states `y` [B, N] and `ph` [B, H]" % (name, mode))
+    _require_f32(y, "y")
+    _require_f32(ph, "ph")
+    B = y.shape[0] if y.dim() == 2 else 0
+    if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
+            y.device != params.device or ph.device != params.device:
+        raise ValueError("%s: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
+                         "parameters' device, got %s and %s" % (name, N, H, tuple(y.shape), tuple(ph.shape)))
+    return y, ph, B
+
+
+def check_network_indices(name, regulator, target, N):
+    """(regulator, target) of a label set as int64 tensors [E], each on the device it came from (the host for lists and
+    numpy arrays); ValueError for arrays of unequal length, of a non-integer dtype or with an index outside [0, N)"""
+    out = []
+    for what, x in (("regulator", regulator), ("target", target)):
+        try:
+            x = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("%s: `%s` must be an array of gene indices" % (name, what))
+        if x.numel() == 0:
+            x = x.to(torch.int64)
+        if x.dim() != 1 or x.dtype in (torch.bool,) or x.is_floating_point() or x.is_complex():
+            raise ValueError("%s: `%s` must be a one-dimensional array of integer gene indices, got %s %s"
+                             % (name, what, x.dtype, tuple(x.shape)))
+        out.append(x.to(torch.int64))
+    r, t = out
+    if r.numel() != t.numel():
+        raise ValueError("%s: regulator and target must have the same length, got %d and %d" % (name, r.numel(), t.numel()))
+    if r.numel():
+        lo, hi = min(int(r.min()), int(t.min())), max(int(r.max()), int(t.max()))
+        if lo < 0 or hi >= N:
+            raise ValueError("%s: gene indices must lie in [0, %d), got %d .. %d" % (name, N, lo, hi))
+    return r, t
+
+
+def _u32(x):
+    """an int64 tensor of values in [0, 2^32) as the int32 tensor with the same low 32 bits (what the kernels read as
+    unsigned)"""
+    return torch.where(x >= 2 ** 31, x - 2 ** 32, x).to(torch.int32)
+
+
+def effects_gather(params, mode, regulator, target, y=None, ph=None, orient=False):
+    """phx_effects_gather on laid-out parameters (`Params`): float32 [E] on the device, element e the entry (regulator[e],
+    target[e]) of the matrix `effects_matrix(params, mode, y, ph)` would return, bit for bit, or with `orient` of its
+    make_mask form (include/phoenix_hip.h).  regulator, target: int64 tensors [E] on the parameters' device with values in
+    [0, N) (check_network_indices); duplicates are allowed.  The keys are grouped by tile with one sort; only the tiles
+    that hold a listed entry are formed."""
+    y, ph, B = _netscore_states("effects_at", params, mode, y, ph)
+    N, dev = params.N, params.device
+    E = regulator.numel()
+    if E == 0:
+        return torch.empty(0, dtype=torch.float32, device=dev)
+    if E >= 2 ** 32:
+        raise ValueError("effects_at: %d entries do not fit one list" % E)
+    T = (N + NETSCORE_TILE - 1) // NETSCORE_TILE
+    tile = torch.div(regulator, NETSCORE_TILE, rounding_mode="floor") * T + torch.div(target, NETSCORE_TILE, rounding_mode="floor")
+    tile, order = torch.sort(tile)
+    keys = _u32((regulator * N + target)[order])
+    bounds = torch.arange(T * T + 1, dtype=torch.int64, device=dev)
+    offsets = _u32(torch.searchsorted(tile, bounds))
+    sorted_values = torch.empty(E, dtype=torch.float32, device=dev)
+    p = params.on_current_stream()
+    _check_call(_lib.load().phx_effects_gather(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B,
+                                               _lib.EDGES_ORIENT if orient else 0, _p(keys), _p(offsets), E, _p(sorted_values),
+                                               _stream_ptr()))
+    values = torch.empty_like(sorted_values)
+    values[order] = sorted_values
+    return values
+
+
+def network_score(params, mode, regulator, target, y=None, ph=None, orient=False, diagonal=False):
+    """The rank statistics of the matrix `effects_matrix(params, mode, y, ph)` (with `orient`: of its make_mask form)
+    against the label set (regulator, target) -- int64 tensors [E] on the parameters' device with values in [0, N) -- without
+    the matrix: (auroc, average_precision, n_positive, n_negative, threshold float32 [m], tp int64 [m], fp int64 [m]),
+    the three arrays on the device (include/phoenix_hip.h: phx_effects_gather, phx_effects_rank_counts).  GATHER reads the
+    positives' values, a sort makes the distinct magnitudes u and their multiplicities, RANK counts every scored entry
+    between and on them, and cumulative sums of the 2 m + 1 counts are the curve.  Everything is integer arithmetic up to
+    the two final float64 divisions."""
+    y, ph, B = _netscore_states("network_score", params, mode, y, ph)
+    N, dev = params.N, params.device
+    key = torch.unique(regulator * N + target)
+    if not diagonal:
+        key = key[key % (N + 1) != 0]                 # i N + i = i (N + 1)
+    n_scored = N * N - (0 if diagonal else N)
+    P = int(key.numel())
+    Nn = n_scored - P
+    if P == 0 or Nn == 0:
+        raise ValueError("network_score: Only one class present in the labels (%d positives, %d negatives); the scores "
+                         "are not defined in that case" % (P, Nn))
+    reg = torch.div(key, N, rounding_mode="floor")
+    values = effects_gather(params, mode, reg, key - reg * N, y=y, ph=ph, orient=orient)
+    mag = values.view(torch.int32) & 0x7FFFFFFF
+    u, mult = torch.unique(mag, return_counts=True)   # ascending
+    m = int(u.numel())
+    lib = _lib.load()
+    nbytes = lib.phx_effects_rank_workspace_bytes(N, params.H, B, _lib.EFFECTS_MODES[mode])
+    wkey = (dev.index, _stream_raw(dev.index), OP_NETSCORE)
+    ws = _ws_cache.get(wkey)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _ws_cache[wkey] = torch.empty(int(nbytes) // 4 + 16, dtype=torch.int32, device=dev)
+    counts = torch.empty(2 * m + 1, dtype=torch.int32, device=dev)
+    p = params.on_current_stream()
+    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
+    _check_call(lib.phx_effects_rank_counts(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, _p(u), m,
+                                            _p(counts), _p(ws), nbytes, _stream_ptr()))
+    bad = int(ws[0].item()) & 0xFFFFFFFF
+    if bad:
+        raise ValueError("network_score: %d scored entries are not finite" % bad)
+    c = counts.to(torch.int64) & 0xFFFFFFFF
+    if int(c.sum()) != n_scored:
+        raise RuntimeError("network_score: the rank pass counted %d entries of %d" % (int(c.sum()), n_scored))
+    # descending thresholds: everything at or above u[k] is the buckets 2 k + 1 ..
+    at, between = c[1::2], c[0::2]                    # at[k] ties with u[k]; between[k] lies below u[k] (between[m]: above all)
+    ge_all = torch.flip(torch.cumsum(torch.flip(at + between[1:], (0,)), 0), (0,))      # entries >= u[k]
+    ge_pos = torch.flip(torch.cumsum(torch.flip(mult, (0,)), 0), (0,))                  # positives >= u[k]
+    gt_pos = ge_pos - mult
+    # U2 = sum over all scored entries of (2 gt + eq) - P^2:  an entry tied with u[k] has gt = gt_pos[k], eq = mult[k]; one
+    # in the gap below u[k] has gt = ge_pos[k], eq = 0; one above all positives has neither
+    U2 = int((at * (2 * gt_pos + mult)).sum() + (between[:m] * (2 * ge_pos)).sum()) - P * P
+    auroc = U2 / (2 * P * Nn)
+    tp = torch.flip(ge_pos, (0,))
+    fp = torch.flip(ge_all, (0,)) - tp
+    hits = torch.flip(mult, (0,)).to(torch.float64)   # tp[k] - tp[k - 1]
+    ap = float((hits / P * (tp.to(torch.float64) / (tp + fp).to(torch.float64))).sum())
+    threshold = torch.flip(u, (0,)).view(torch.float32)
+    return auroc, ap, P, Nn, threshold, tp, fp
