@@ -212,7 +212,12 @@ int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t, in
  * phx_debug_backprop_launches(N, H, B, T, method) == 1, else the chunk the shared driver walks the batch in); 0: no kernel
  * plans the shape.  Sized for 256 CUs when no device is visible.  K = 0 when the call has no step size.
  * phx_debug_backprop_kernel_m: 5 = k1_solve_bp serves the shape, 0 = refused.  phx_debug_backprop_launches: launches of
- * that kernel one call makes (0: refused). */
+ * that kernel one call makes (0: refused).
+ * phx_debug_backprop_plan: the launch geometry of the FIRST launch of the batch, plan[0..7] = HT (hidden tiles of 16 rows),
+ * NB (gene blocks of 32 a workgroup keeps in LDS), G (workgroups that share one trajectory tile = ceil(nblk / NB)), TG (batch
+ * groups), ntg (trajectory tiles of 16 per group), nblk, chunk_rows (rows per launch) and launches.  Returns 1 with a plan,
+ * 0 without one (plan zeroed: dopri5, H > 128, PHX_ENGINE=v0).  cus <= 0: the CU count of the current device; a positive
+ * `cus` plans for that many CUs and needs no device.  TG * G <= cus always. */
 size_t phx_odeint_backprop_workspace_bytes(int N, int H, int B, int T, long long grid_steps);
 int phx_odeint_backprop_backward(const phx_params *p, const double *t, int B, int T, const phx_solve_opts *opts,
                                  const float *y_saved, const float *grad_y, float *adj_y0, const phx_grads *grads,
@@ -220,6 +225,7 @@ int phx_odeint_backprop_backward(const phx_params *p, const double *t, int B, in
                                  void *stream, double step_size, long long grid_steps);
 int phx_debug_backprop_kernel_m(int N, int H, int B, int T, int method);
 int phx_debug_backprop_launches(int N, int H, int B, int T, int method);
+int phx_debug_backprop_plan(int cus, int N, int H, int B, int T, int method, int *plan);
 
 /* prior_grad = X[K,N] @ P[N,N] with the prior matrix P in CSC form
  * (colptr [N+1], rowidx/vals [nnz], rows ascending inside a column).  Replaces the reference's dense

@@ -33,6 +33,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_layout_params", "phx_debug_forward_kernel_m", "phx_debug_queue_kernel_events", "phx_debug_solve_launches",
            "phx_odeint_stepped", "phx_odeint_adjoint_backward_stepped", "phx_odeint_backprop_backward",
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
+           "phx_debug_backprop_plan",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
            "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
            "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges",
@@ -92,6 +93,7 @@ def load():
     lib.phx_odeint_backprop_workspace_bytes.restype = C.c_size_t
     lib.phx_debug_backprop_kernel_m.argtypes = [C.c_int] * 5
     lib.phx_debug_backprop_launches.argtypes = [C.c_int] * 5
+    lib.phx_debug_backprop_plan.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int)]
     lib.phx_prior_targets.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.phx_prior_targets_sell.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.phx_prior_mse.argtypes = [C.POINTER(PhxParams), vp, vp, C.c_int, vp, vp, vp, C.c_size_t, vp]

@@ -112,6 +112,12 @@ int bp_chunk(int cus, int N, int H, int B, int T)
     return 0;
 }
 
+// the plan of ONE launch of B rows on `cus` CUs (diagnostic: phx_debug_backprop_plan)
+bool bp_plan(int cus, int N, int H, int B, int T, D1 *out)
+{
+    return plan_bp_cus(cus, N, H, B, T, out);
+}
+
 // workspace bytes in front of the checkpoint region: the largest layout among the launches of the batch
 size_t bp_base_bytes(int cus, int N, int H, int B, int T)
 {

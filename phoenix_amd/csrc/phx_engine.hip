@@ -1669,6 +1669,23 @@ int phx_debug_backprop_launches(int N, int H, int B, int T, int method)
     return (B + chunk - 1) / chunk;
 }
 
+int phx_debug_backprop_plan(int cus, int N, int H, int B, int T, int method, int *plan)
+{
+    if (plan)
+        for (int i = 0; i < 8; ++i) plan[i] = 0;
+    if (N <= 0 || H <= 0 || B <= 0 || T < 1 || method < PHX_EULER || method > PHX_RK4) return 0;
+    if (cus <= 0) cus = num_cus();
+    if (cus <= 0) return 0;                        // no device to ask
+    const int chunk = bp_chunk(cus, N, H, B, T);
+    D1 d;
+    if (chunk <= 0 || !bp_plan(cus, N, H, std::min(chunk, B), T, &d)) return 0;
+    if (plan) {
+        const int v[8] = {d.HT, d.NB, d.G, d.TG, d.ntg, d.nblk, chunk, (B + chunk - 1) / chunk};
+        for (int i = 0; i < 8; ++i) plan[i] = v[i];
+    }
+    return 1;
+}
+
 size_t phx_odeint_backprop_workspace_bytes(int N, int H, int B, int T, long long grid_steps)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 1 || grid_steps < 0) return 0;

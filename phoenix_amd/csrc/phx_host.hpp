@@ -219,9 +219,10 @@ bool plan_fwd3_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out
 bool plan_fwd3c_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out);
 // k1_solve_bp (backpropagation through the fixed-grid steps): not in the lists of the adjoint direction, it has entry
 // points of its own.  bp_chunk: rows per launch of a batch (0: no plan); bp_base_bytes: workspace in front of the
-// checkpoint region; both size for 256 CUs when cus <= 0 (no device in sight).
+// checkpoint region; both size for 256 CUs when cus <= 0 (no device in sight).  bp_plan: the plan of one launch of B rows.
 const Backend &bp_backend();
 int bp_chunk(int cus, int N, int H, int B, int T);
+bool bp_plan(int cus, int N, int H, int B, int T, D1 *out);
 size_t bp_base_bytes(int cus, int N, int H, int B, int T);
 
 }  // namespace phxh

@@ -15,7 +15,7 @@ from conftest import load_golden, relerr, sub
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("Ws", "bs", "Wp", "bp", "Wa", "g")
 NEW = ("phx_odeint_backprop_backward", "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m",
-       "phx_debug_backprop_launches")
+       "phx_debug_backprop_launches", "phx_debug_backprop_plan")
 
 
 def test_new_exports_in_header_and_binding():
@@ -72,6 +72,64 @@ def test_workspace_bytes_formula(N, H, B):
         assert got > prev
         prev = got
     assert lib.phx_odeint_backprop_workspace_bytes(N, 200, B, 5, 3) == 0      # H > 128: no kernel plans the shape
+
+
+def bp_plan(N, H, B, T=5, method="rk4", cus=256):
+    """phx_debug_backprop_plan as a dict (None: no plan); cus = 256 needs no device"""
+    from phoenix_amd import _lib
+    plan = (C.c_int * 8)()
+    if _lib.load().phx_debug_backprop_plan(cus, N, H, B, T, _lib.METHODS[method], plan) == 0:
+        assert list(plan) == [0] * 8
+        return None
+    return dict(zip(("HT", "NB", "G", "TG", "ntg", "nblk", "chunk_rows", "launches"), plan))
+
+
+# the launch geometries tests/test_backprop_geometry_gpu.py is there for, on the 256 CUs of an MI355X
+GEOMETRY = {
+    "g1": ((32, 6, 5), dict(HT=3, NB=1, G=1, TG=1, ntg=1, nblk=1, launches=1)),
+    "g17": ((530, 12, 5), dict(HT=3, NB=1, G=17, TG=1, ntg=1, nblk=17, launches=1)),
+    "g35": ((1100, 12, 20), dict(HT=3, NB=1, G=35, TG=1, ntg=2, nblk=35, launches=1)),
+    "nb2": ((350, 40, 1530), dict(HT=3, NB=2, G=6, TG=24, ntg=4, nblk=11, launches=1)),
+    "nbmax": ((1000, 34, 4096), dict(HT=3, NB=8, G=4, TG=64, ntg=4, nblk=32, launches=1)),      # H = 34: the widest with NB = 8
+    "nb4x2": ((1000, 40, 4096), dict(HT=3, NB=4, G=8, TG=32, ntg=4, nblk=32, chunk_rows=2048, launches=2)),
+    "nb_ht8": ((350, 100, 1530), dict(HT=8, NB=2, G=6, TG=24, ntg=4, nblk=11, launches=1)),
+    "pad": ((200, 100, 70), dict(HT=8, NB=1, G=7, TG=2, ntg=4, nblk=7, launches=1)),
+    "b4136": ((350, 40, 4096 + 40), dict(HT=3, NB=4, G=3, TG=65, ntg=4, nblk=11, launches=1)),   # last group: 40 rows
+    "chunk": ((700, 40, 4096 + 40), dict(HT=3, NB=6, G=4, TG=64, ntg=4, nblk=22, chunk_rows=4096, launches=2)),
+    "chunk_tail": ((700, 40, 40), dict(HT=3, NB=1, G=22, TG=1, ntg=3, nblk=22, launches=1)),
+}
+
+
+def test_backprop_plan_on_256_cus(monkeypatch):
+    """phx_debug_backprop_plan with cus = 256 given (no device): the geometry of every case of the GPU file, the planner's
+    invariants over seeded random shapes, and the calls without a plan"""
+    for name, ((N, H, B), want) in sorted(GEOMETRY.items()):
+        got = bp_plan(N, H, B)
+        assert got is not None, name
+        assert {k: got[k] for k in want} == want, (name, got)
+    # nb_ht8: the smallest multiple of 64 minus 6 whose plan keeps two gene blocks per workgroup at H = 100
+    (N, H, B), _ = GEOMETRY["nb_ht8"]
+    assert B % 64 == 58
+    for b in range(58, B, 64):
+        assert bp_plan(N, H, b)["NB"] == 1, b
+    r = np.random.RandomState(20)
+    for _ in range(200):
+        N, H, B = int(r.randint(1, 3001)), int(r.randint(1, 129)), int(r.randint(1, 8193))
+        d = bp_plan(N, H, B)
+        assert d is not None, (N, H, B)                  # a chunk of 16 rows needs ceil(N / 32) <= 94 workgroups
+        ntt = -(-min(B, d["chunk_rows"]) // 16)          # trajectory tiles of the first launch
+        assert d["HT"] == (3 if H <= 48 else 8) and d["nblk"] == -(-N // 32) and 1 <= d["NB"] <= 8, (N, H, B, d)
+        assert d["TG"] * d["G"] <= 256, (N, H, B, d)
+        assert d["NB"] * d["G"] >= d["nblk"] > (d["G"] - 1) * d["NB"], (N, H, B, d)
+        assert d["TG"] == -(-ntt // 4) and d["ntg"] == (ntt if d["TG"] == 1 else 4), (N, H, B, d)
+        assert d["launches"] == -(-B // d["chunk_rows"]), (N, H, B, d)
+        assert d["chunk_rows"] == B or d["chunk_rows"] in (4096, 2048, 1024, 512, 256, 128, 64, 32, 16), (N, H, B, d)
+    assert bp_plan(350, 40, 64, method="dopri5") is None
+    assert bp_plan(350, 129, 64) is None and bp_plan(350, 128, 64) is not None
+    assert bp_plan(0, 40, 64) is None and bp_plan(350, 40, 0) is None
+    assert bp_plan(350, 40, 1024, method="euler") == bp_plan(350, 40, 1024, method="midpoint") == bp_plan(350, 40, 1024)
+    monkeypatch.setenv("PHX_ENGINE", "v0")               # the forced VALU engine (read whenever the planner runs)
+    assert bp_plan(350, 40, 64) is None
 
 
 class TorchNet(torch.nn.Module):
