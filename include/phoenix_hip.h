@@ -381,6 +381,35 @@ int phx_effects_gather(const phx_params *p, int mode, const float *y, const floa
 int phx_effects_rank_counts(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, const unsigned *u,
                             unsigned m, unsigned *counts, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Every gene's k strongest regulators or targets in those matrices, with its degree and weighted degree, without the
+ * matrices: M = what phx_effects_matrix writes for (mode, y, ph, B).  Entry M[i,j] (regulator i -> target j) is eligible
+ * under the rules of phx_effects_edges (finite and non-zero on m = bits & 0x7fffffff; i != j unless PHX_EDGES_DIAGONAL; with
+ * PHX_EDGES_ORIENT |M[i,j]| > |M[j,i]| strictly, never the diagonal, a NaN partner loses) and, in addition, when
+ * regulator_ok[i] != 0, target_ok[j] != 0 (unsigned char [N] each; null: every gene) and |M[i,j]| >= tau (tau = +0: no
+ * threshold).  axis = PHX_NEIGHBORS_OF_TARGET: line n is column n, the regulators of target n; PHX_NEIGHBORS_OF_REGULATOR:
+ * line n is row n, the targets of regulator n.  For every line n < N:
+ *   gene  [N, k], value [N, k]   the k strongest eligible entries of the line: the OTHER gene's index and the entry with the
+ *                                bits phx_effects_matrix writes, by magnitude descending, then by that index ascending;
+ *                                a line with fewer than k eligible entries is padded with gene = -1, value = +0.
+ *   count [N]                    the eligible entries of the line (the in- or out-degree at tau): an exact integer.
+ *   strength [N]                 the float sum of their magnitudes (the weighted degree).
+ * phx_neighbors.hip: a workgroup owns 64 lines and streams the 64 x 64 tiles of the other dimension through the tile engine
+ * of phx_effects_matrix (with ORIENT the partner tile too), selecting in the epilogue; the streamed dimension is cut into S
+ * segments, S a function of N alone (PHX_NEIGHBORS_SEGMENTS=<n> in the environment, read per call, forces n; S <= 8 and
+ * <= ceil(N / 64) always), whose lists, counts and sums a second small kernel merges in segment order.  No atomics: the
+ * lists are sets selected by a total order, every float sum has an order fixed by (N, S), so all four results are bitwise
+ * reproducible.  A line tile or a streamed tile without a candidate is not formed.  Nothing allocates or synchronises.
+ * PHX_ERR_BAD_ARG before any device call: null p / Ws / Wp / WaT / g, N < 2, N > 65535 (a gene index is 16 bits of the key),
+ * H < 1, H > 256, an unknown mode, a Jacobian mode with null y or ph or B < 1, unknown flags, an unknown axis, k < 1, k > 64,
+ * tau negative, not finite or -0, a null result.  PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_effects_neighbors_workspace_bytes(N, H, B, mode, axis, k) (0 for arguments the call refuses; it reads the same
+ * environment switch). */
+enum phx_neighbors_axis { PHX_NEIGHBORS_OF_REGULATOR = 0, PHX_NEIGHBORS_OF_TARGET = 1 };
+size_t phx_effects_neighbors_workspace_bytes(int N, int H, int B, int mode, int axis, int k);
+int phx_effects_neighbors(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, int axis, int k,
+                          float tau, const unsigned char *regulator_ok, const unsigned char *target_ok, int *gene, float *value,
+                          unsigned *count, float *strength, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

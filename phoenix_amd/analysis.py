@@ -178,6 +178,78 @@ def effects_edges(odenet, top=None, threshold=None, orient=False, diagonal=False
                                            orient=orient, diagonal=diagonal, max_edges=max_edges))
 
 
+Neighbors = collections.namedtuple("Neighbors", ("gene", "value", "count", "strength"))
+
+
+def effects_neighbors(odenet, k, of="target", regulators=None, targets=None, threshold=None, orient=False, diagonal=False,
+                      y=None, reduce="mean_abs"):
+    """Every gene's k strongest regulators (of="target": line j is column j of the matrix) or targets (of="regulator": line i
+    is row i) in `effects_matrix(odenet)` (y=None) or `jacobian_matrix(odenet, y, reduce)`, without the [N, N] matrix:
+    Neighbors(gene int64 [N, k], value float32 [N, k], count int64 [N], strength float32 [N]) on the device.  `gene` is the
+    other gene's index, the entries of a line are sorted by |value| descending, then by that index; every value has the bits
+    of the matrix entry; a line with fewer than k eligible entries is padded with gene = -1, value = +0.  `count` is the
+    number of eligible entries of the line (with `threshold`: the in- or out-degree at that threshold), `strength` the
+    float32 sum of their magnitudes (the weighted degree).
+    Eligible are the entries `effects_edges` admits -- finite, non-zero, off the diagonal unless `diagonal=True`, with
+    `orient=True` only the strictly stronger direction of a gene pair -- whose regulator is in `regulators` and whose target
+    is in `targets` (sequences or tensors of gene indices, duplicates count once, None: all genes; e.g. a transcription-factor
+    list, as get_link_list of GRN_rnaode.py:43-181 takes one) and, with `threshold` (positive, finite), |value| >= threshold.
+    1 <= k <= 64.  One kernel call; the results are bitwise reproducible."""
+    if y is not None and reduce not in ("mean", "mean_abs"):
+        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
+    tensors = params_of(odenet)
+    k, _, regulators, targets = engine.check_neighbors_selection(k, of, regulators, targets, threshold, tensors[0].shape[1])
+    engine._require_gpu(tensors[0], "odenet")
+    with torch.no_grad():
+        p = engine.params_cached(*tensors)
+        y2, ph = (None, None) if y is None else _states(p, y)
+        return Neighbors(*engine.effects_neighbors(p, "effects" if y is None else reduce, k, of=of, y=y2, ph=ph,
+                                                   regulators=regulators, targets=targets, threshold=threshold,
+                                                   orient=orient, diagonal=diagonal))
+
+
+def write_link_list(fp, edges, gene_names=None, signed=False, of=None):
+    """Writes the reference's ranked link-list file (get_link_list, GRN_rnaode.py:140-163): one line "regulator<TAB>target<TAB>
+    score" per link, the score as %.6f.  `edges`: an `Edges`, written in its order, or a `Neighbors` together with the `of` it
+    was made with ("target" / "regulator"), written line by line in its own order without the padding entries.  `gene_names`
+    (one per gene, in row order) names the genes; without it they are written as G<index + 1>, the reference's default.  The
+    score is |value|, or the value itself with `signed=True`.  `fp`: a path or an open text file.  Returns the number of
+    links written."""
+    if isinstance(edges, Neighbors):
+        if of not in ("target", "regulator"):
+            raise ValueError('write_link_list: a Neighbors needs of="target" or of="regulator", got %r' % (of,))
+        gene = np.asarray(edges.gene.cpu() if isinstance(edges.gene, torch.Tensor) else edges.gene).astype(np.int64)
+        value = np.asarray(edges.value.cpu() if isinstance(edges.value, torch.Tensor) else edges.value)
+        line = np.broadcast_to(np.arange(gene.shape[0], dtype=np.int64)[:, None], gene.shape)
+        keep = gene >= 0
+        other, line, value = gene[keep], line[keep], value[keep]
+        regulator, target = (other, line) if of == "target" else (line, other)
+    elif isinstance(edges, Edges):
+        if of is not None:
+            raise ValueError("write_link_list: `of` belongs to a Neighbors")
+        regulator, target, value = (np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x) for x in edges)
+    else:
+        raise ValueError("write_link_list: `edges` must be an Edges or a Neighbors, got %s" % type(edges).__name__)
+    if gene_names is not None:
+        gene_names = [str(n) for n in gene_names]
+        if len(value) and max(int(regulator.max()), int(target.max())) >= len(gene_names):
+            raise ValueError("write_link_list: %d gene names do not cover gene index %d"
+                             % (len(gene_names), max(int(regulator.max()), int(target.max()))))
+    score = value.astype(np.float64) if signed else np.abs(value.astype(np.float64))
+    lines = []
+    for i, j, s in zip(regulator.tolist(), target.tolist(), score.tolist()):
+        if gene_names is not None:
+            lines.append("%s\t%s\t%.6f\n" % (gene_names[i], gene_names[j], s))
+        else:
+            lines.append("G%d\tG%d\t%.6f\n" % (i + 1, j + 1, s))
+    if hasattr(fp, "write"):
+        fp.write("".join(lines))
+    else:
+        with open(fp, "w") as f:
+            f.write("".join(lines))
+    return len(lines)
+
+
 def read_network(fp, gene_names):
     """Host parser of the reference's edge files (breast_cancer_data/clean_data/validation_network.csv, the simulator's
     edge_properties_G*.csv): a header row, then the regulator's and the target's gene name in the first two columns, quoted

@@ -835,6 +835,85 @@ def effects_edges(params, mode, y=None, ph=None, top=None, threshold=None, orien
     return torch.div(flat, N, rounding_mode="floor"), flat % N, values[order]
 
 
+OP_NEIGHBORS = 9     # workspace-cache key of effects_neighbors (phx_effects_neighbors_workspace_bytes sizes it)
+
+
+def _gene_set(name, what, x, N):
+    """a candidate list (`regulators` / `targets` of `effects_neighbors`) as a one-dimensional int64 tensor on the device
+    it came from, or None for all genes; ValueError for anything but integer gene indices inside [0, N)"""
+    if x is None:
+        return None
+    try:
+        x = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x if hasattr(x, "shape") else list(x)))
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError("%s: `%s` must be a sequence of gene indices" % (name, what))
+    if x.numel() == 0:
+        x = x.reshape(-1).to(torch.int64)
+    if x.dim() != 1 or x.dtype == torch.bool or x.is_floating_point() or x.is_complex():
+        raise ValueError("%s: `%s` must be a one-dimensional sequence of integer gene indices, got %s %s"
+                         % (name, what, x.dtype, tuple(x.shape)))
+    x = x.to(torch.int64)
+    if x.numel() and (int(x.min()) < 0 or int(x.max()) >= N):
+        raise ValueError("%s: `%s` must lie in [0, %d), got %d .. %d" % (name, what, N, int(x.min()), int(x.max())))
+    return x
+
+
+def check_neighbors_selection(k, of, regulators, targets, threshold, N):
+    """the ValueErrors of the selection arguments of `effects_neighbors`, raised before a device is needed: (k, axis,
+    regulators, targets) with the candidate lists as int64 tensors or None"""
+    name = "effects_neighbors"
+    if not _is_int(k) or not 1 <= k <= _lib.NEIGHBORS_MAX_K:
+        raise ValueError("%s: k must be an integer in [1, %d], got %r" % (name, _lib.NEIGHBORS_MAX_K, k))
+    if not isinstance(of, str) or of not in _lib.NEIGHBORS_AXES:
+        raise ValueError('%s: of must be "target" or "regulator", got %r' % (name, of))
+    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and
+                                      not isinstance(threshold, bool) and threshold > 0 and np.isfinite(threshold)):
+        raise ValueError("%s: threshold must be positive and finite, got %r" % (name, threshold))
+    return int(k), _lib.NEIGHBORS_AXES[of], _gene_set(name, "regulators", regulators, N), _gene_set(name, "targets", targets, N)
+
+
+def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=None, targets=None, threshold=None,
+                      orient=False, diagonal=False):
+    """phx_effects_neighbors on laid-out parameters (`Params`): for every line of the matrix `effects_matrix(params, mode, y,
+    ph)` would return -- column n with of="target", row n with of="regulator" -- the k strongest eligible entries
+    (include/phoenix_hip.h) as (gene int64 [N, k], value float32 [N, k], count int64 [N], strength float32 [N]) on the
+    device.  `regulators` / `targets`: candidate gene indices (None: all), turned into byte masks on the device.  One call:
+    the matrix is not formed."""
+    k, axis, regulators, targets = check_neighbors_selection(k, of, regulators, targets, threshold, params.N)
+    y, ph, B = _netscore_states("effects_neighbors", params, mode, y, ph)
+    N, H, dev = params.N, params.H, params.device
+    tau = 0.0
+    if threshold is not None:
+        tau = _edges_tau(float(threshold))
+        if tau is None:                                   # above every finite float32: nothing is eligible
+            return (torch.full((N, k), -1, dtype=torch.int64, device=dev), torch.zeros((N, k), dtype=torch.float32, device=dev),
+                    torch.zeros(N, dtype=torch.int64, device=dev), torch.zeros(N, dtype=torch.float32, device=dev))
+    masks = []
+    for idx in (regulators, targets):
+        if idx is None:
+            masks.append(None)
+        else:
+            m = torch.zeros(N, dtype=torch.uint8, device=dev)
+            m[idx.to(dev)] = 1
+            masks.append(m)
+    lib = _lib.load()
+    nbytes = lib.phx_effects_neighbors_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode], axis, k)
+    wkey = (dev.index, _stream_raw(dev.index), OP_NEIGHBORS)
+    ws = _ws_cache.get(wkey)
+    if ws is None or ws.numel() < nbytes:
+        ws = _ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    gene = torch.empty((N, k), dtype=torch.int32, device=dev)
+    value = torch.empty((N, k), dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    strength = torch.empty(N, dtype=torch.float32, device=dev)
+    p = params.on_current_stream()
+    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
+    _check_call(lib.phx_effects_neighbors(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, axis, k, tau,
+                                          _p(masks[0]), _p(masks[1]), _p(gene), _p(value), _p(count), _p(strength), _p(ws),
+                                          nbytes, _stream_ptr()))
+    return gene.to(torch.int64), value, count.to(torch.int64), strength
+
+
 OP_NETSCORE = 8      # workspace-cache key of network_score (phx_effects_rank_workspace_bytes sizes it)
 NETSCORE_TILE = 64   # the tile by which phx_effects_gather wants its keys grouped
 
