@@ -14,16 +14,51 @@ def fAct(TF, EC50=0.5, n=1.39):
     return B * TF ** n / (K_n + TF ** n)
 
 
-def rhs(names, expressions, x):
+def fAct0(TF, EC50=0.5, n=1.39):
+    """`fAct` continued to TF <= 0 by TF^n := 0, which is what the device interpreter (csrc/phx_hill.inc) and
+    `interpret_programs` below define there; R and `fAct` give NaN for a negative TF and a fractional n.  For TF > 0
+    the operations, and so the bits, are those of `fAct`.  TF: an array or a Python float."""
+    B = (EC50 ** n - 1) / (2 * EC50 ** n - 1)
+    K_n = B - 1
+    if isinstance(TF, float):
+        tn = TF ** n if TF > 0 else 0.0
+    else:
+        TF = np.asarray(TF, np.float64)
+        tn = np.where(TF > 0, np.abs(TF) ** n, 0.0)
+    return B * tn / (K_n + tn)
+
+
+def compile_rhs(names, expressions, fact=fAct):
+    """`rhs` with the expression strings compiled once: returns f(x, rowwise=False) -> rates, for callers that evaluate
+    many states of one network (an RK4 restatement); `fact` is the function the strings' `fAct` is bound to.
+    rowwise=True evaluates the strings once per row of x on Python floats instead of once on numpy columns: the same float64
+    arithmetic, several times faster for a handful of rows (`fact` must take a float then)."""
+    codes = [None if e.strip() == "input gene" else compile(e, "<eqn %s>" % names[g], "eval")
+             for g, e in enumerate(expressions)]
+    live = [(g, c) for g, c in enumerate(codes) if c is not None]
+
+    def f(x, rowwise=False):
+        x = np.asarray(x, np.float64)
+        out = np.zeros_like(x)
+        if rowwise:
+            xr, outr = x.reshape(-1, x.shape[-1]), out.reshape(-1, x.shape[-1])
+            for b in range(xr.shape[0]):
+                env = dict(zip(names, xr[b].tolist()))
+                env["fAct"] = fact
+                outr[b, [g for g, _ in live]] = [eval(c, {"__builtins__": {}}, env) for _, c in live]
+            return out
+        env = {n: x[..., i] for i, n in enumerate(names)}
+        env["fAct"] = fact
+        for g, c in live:
+            out[..., g] = eval(c, {"__builtins__": {}}, env)
+        return out
+
+    return f
+
+
+def rhs(names, expressions, x, fact=fAct):
     """rates of every gene at the states x [..., N] ('input gene' rows: 0)."""
-    x = np.asarray(x, np.float64)
-    env = {n: x[..., i] for i, n in enumerate(names)}
-    env["fAct"] = fAct
-    out = np.zeros_like(x)
-    for g, e in enumerate(expressions):
-        if e.strip() != "input gene":
-            out[..., g] = eval(compile(e, "<eqn %s>" % names[g], "eval"), {"__builtins__": {}}, env)
-    return out
+    return compile_rhs(names, expressions, fact)(x)
 
 
 def simulate(names, expressions, x0, times, rtol=1e-10, atol=1e-12):
@@ -39,10 +74,12 @@ def simulate(names, expressions, x0, times, rtol=1e-10, atol=1e-12):
     return sol.y.T
 
 
-def interpret_programs(code, consts, off, length, x):
+def interpret_programs(code, consts, off, length, x, dtype=np.float64):
     """fp64 interpreter of the postfix programs phoenix_amd.simulator compiles (same opcodes as csrc/phx_hill.inc):
-    checks the COMPILER against `rhs` above without a GPU."""
-    x = np.asarray(x, np.float64)
+    checks the COMPILER against `rhs` above without a GPU.  dtype=np.float32 runs every operation in fp32 (states and
+    constants rounded first, as the device holds them): the rounding error a correct fp32 interpreter may show."""
+    x = np.asarray(x, dtype)
+    consts = np.asarray(consts, dtype)
     out = np.zeros_like(x)
     for g in range(len(off)):
         st = []
@@ -55,7 +92,7 @@ def interpret_programs(code, consts, off, length, x):
                 st[-1] = -st[-1]
             elif op == 7:
                 b, k, n = consts[arg: arg + 3]
-                tn = np.where(st[-1] > 0, np.abs(st[-1]) ** n, 0.0)
+                tn = np.where(st[-1] > 0, np.abs(st[-1]) ** n, dtype(0))
                 st[-1] = b * tn / (k + tn)
             else:
                 r = st.pop()

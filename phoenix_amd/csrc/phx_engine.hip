@@ -1500,7 +1500,8 @@ int phx_hill_rhs(const int *code, const int *off, const int *len, const float *c
 {
     if (!code || !off || !len || !consts || !x || !out || B <= 0 || N <= 0) return PHX_ERR_BAD_ARG;
     const HillProg p{reinterpret_cast<const int2 *>(code), off, len, consts};
-    hipLaunchKernelGGL(k_hill_rhs, dim3((N + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, p, x, out, B, N);
+    const dim3 grid((N + 255) / 256, std::min(B, 2048));   // the kernel strides over the rows, as k_prior_spmm does
+    hipLaunchKernelGGL(k_hill_rhs, grid, dim3(256), 0, (hipStream_t)stream, p, x, out, B, N);
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
 }
 

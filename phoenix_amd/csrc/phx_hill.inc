@@ -47,8 +47,10 @@ __device__ __forceinline__ float hill_eval(const HillProg &p, int gene, const fl
 
 __global__ void k_hill_rhs(HillProg p, const float *__restrict__ x, float *__restrict__ out, int B, int N)
 {
-    const int gene = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (gene < N && b < B) out[(long long)b * N + gene] = hill_eval(p, gene, x + (long long)b * N);
+    const int gene = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gene >= N) return;
+    // rows are strided over gridDim.y (capped by the host), so B is not bounded by the 65 535 limit of a grid's y dimension
+    for (int b = blockIdx.y; b < B; b += gridDim.y) out[(long long)b * N + gene] = hill_eval(p, gene, x + (long long)b * N);
 }
 
 // One workgroup per sample, the sample's state in LDS, classical RK4 with equal sub-steps <= dt_max between the

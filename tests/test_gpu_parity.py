@@ -1347,6 +1347,10 @@ def test_f1_prior_targets_spmm(pa, dev):
     dense = Pb.to_dense().to(dev)
     ref = torch.matmul(X[:64], dense)
     assert relerr(out[:64].cpu().numpy(), ref.cpu().numpy()) < 5e-6
+    # ... and the last 64 rows: K = 10000 with three rows per tile (N = 11165) ends in a one-row tail at row 9999, and every
+    # row from 3 * 4 * CUs up is a second pass of the kernel's grid-stride loop
+    ref_last = torch.matmul(X[-64:], dense)
+    assert relerr(out[-64:].cpu().numpy(), ref_last.cpu().numpy()) < 5e-6
     # linearity property at full size: (X1 + X2) P = X1 P + X2 P
     X2 = torch.rand(K, 1, N, device=dev) - 0.5
     lhs = prior_targets(X + X2, Pb)

@@ -239,3 +239,135 @@ def test_equation_structure_of_the_690_gene_network_matches_its_edge_table():
             assert (edges[(tf, node)]["activation"] == "FALSE") == neg, (tf, node)
         n += 1
     assert n == 593
+
+
+# --------------------------------------------------------------------------- synthetic networks (shared with
+# tests/test_simulator_gpu.py): any size, from the project's own equation builder, plus two hand-written genes for what
+# the shipped text never has -- the deepest evaluation stack the device interpreter holds, and the unary operators
+CHAIN = 24          # activations of the deep gene = MAX_STACK (HILL_STACK in csrc/phx_hill.inc)
+_NETWORKS = {}
+
+
+def and_chain(node, regulators, edges):
+    """right-nested AND over the regulators: (a1 * (a2 * (... * aL)))"""
+    tree = ("node", regulators[-1])
+    for tf in reversed(regulators[:-1]):
+        tree = ("and", ("node", tf), tree)
+    return tree
+
+
+def compiled_depth(names, expr):
+    import ast
+    from phoenix_amd.simulator import _Compiler
+    c = _Compiler({n: i for i, n in enumerate(names)})
+    c.visit(ast.parse(expr, mode="eval"))
+    return c.max_depth, len(c.code)
+
+
+def synthetic_network(N, seed=0):
+    """Seeded N-gene network: about 20 % "input gene" rows; every other gene gets 1-4 random regulators joined by random
+    and / or / not, written by `simulator.rate_expression`; edge weights U(0.5, 1), n U(1.39, 3), EC50 U(0.25, 0.5), so
+    EC50^n < 0.45, K_n > 0 and K_n + TF^n cannot vanish.  The last two genes are hand-written: `DEEP`, a right-nested AND
+    chain of CHAIN activations (weight 1) of the genes `info["chain_regs"]`, which needs an evaluation stack of exactly
+    MAX_STACK, and `UNARY`, whose text has unary minus (of a constant and of a term), unary plus and a division by a
+    constant.  Returns (names, expressions, info); cached, the lists are not to be modified."""
+    if (N, seed) in _NETWORKS:
+        return _NETWORKS[(N, seed)]
+    from phoenix_amd import simulator as sim
+    assert N >= 12
+    rs = np.random.RandomState(500 + seed + N)
+    names = ["G%d" % i for i in range(N - 2)] + ["DEEP", "UNARY"]
+    is_input = rs.rand(N) < 0.2
+    is_input[N - 2:] = False
+    edges = {}
+
+    def edge(tf, node, weight=None):
+        w, n, ec50 = rs.uniform(0.5, 1.0), rs.uniform(1.39, 3.0), rs.uniform(0.25, 0.5)
+        assert ec50 ** n < 0.45 and sim.fact_constants(ec50, n)[1] > 0            # K_n > 0
+        edges[(tf, node)] = {"from": tf, "weight": weight or "%.9g" % w, "EC50": "%.9g" % ec50, "n": "%.9g" % n}
+
+    def logic(regs):
+        t = ("node", regs[0]) if rs.rand() < 0.7 else ("not", ("node", regs[0]))
+        for tf in regs[1:]:
+            u = ("node", tf) if rs.rand() < 0.7 else ("not", ("node", tf))
+            t = ("and" if rs.rand() < 0.5 else "or", t, u) if rs.rand() < 0.5 else ("or" if rs.rand() < 0.5 else "and", u, t)
+            if rs.rand() < 0.15:
+                t = ("not", t)
+        return t
+
+    exprs = []
+    for g in range(N - 2):
+        if is_input[g]:
+            exprs.append("input gene")
+            continue
+        regs = [names[i] for i in np.unique(rs.randint(0, N, rs.randint(1, 5)))]      # itself, DEEP and UNARY included
+        for tf in regs:
+            edge(tf, names[g])
+        exprs.append(sim.rate_expression(names[g], logic(regs), edges))
+    chain_regs = [names[i] for i in rs.choice(N - 2, CHAIN, replace=N - 2 < CHAIN)]   # a tiny network repeats some
+    for tf in chain_regs:
+        edge(tf, "DEEP", weight="1")
+    exprs.append(sim.rate_expression("DEEP", and_chain("DEEP", chain_regs, edges), edges))
+    a, b = names[int(rs.randint(0, N - 2))], names[int(rs.randint(0, N - 2))]
+    exprs.append("(-(-0.9 * fAct(%s, 0.31, 2.2) + +%s) / 2.5 + 0.6 - UNARY) / 1.25" % (a, b))
+    assert compiled_depth(names, exprs[N - 2]) == (sim.MAX_STACK, 127) and CHAIN == sim.MAX_STACK
+    info = {"is_input": is_input, "chain_regs": np.array([names.index(t) for t in chain_regs]), "deep": N - 2,
+            "unary": N - 1}
+    from oracle import hill_oracle
+    rates = hill_oracle.rhs(names, exprs, synthetic_states(N, 3, info, seed), fact=hill_oracle.fAct0)
+    assert np.all(np.isfinite(rates)) and np.all(rates[:, is_input] == 0)
+    assert 0.15 < is_input.mean() < 0.25 or N < 200
+    _NETWORKS[(N, seed)] = (names, exprs, info)
+    return names, exprs, info
+
+
+def synthetic_states(N, B, info, seed=0):
+    """fp32 states from U(-0.2, 1.2), so that TF <= 0 (fAct = 0 there) and TF > 1 both occur; the regulators of DEEP are
+    drawn from U(0.8, 1.2) instead: with one factor of its 24-fold product at zero in six rows of seven, the deep gene
+    would test nothing"""
+    rs = np.random.RandomState(900 + seed + N + 13 * B)
+    x = rs.uniform(-0.2, 1.2, (B, N))
+    x[:, info["chain_regs"]] = rs.uniform(0.8, 1.2, (B, CHAIN))
+    return x.astype(np.float32)
+
+
+def test_synthetic_network_programs_match_the_expression_strings():
+    """the compiler at the opcodes and the stack depth the shipped text never reaches: `interpret_programs` over the
+    compiled 1025-gene synthetic network (deep chain and unary gene included) against Python's evaluation of the strings"""
+    from oracle import hill_oracle
+    from phoenix_amd.simulator import OPS, HillSystem
+    names, exprs, info = synthetic_network(1025)
+    sys_ = HillSystem(names, exprs, device="cpu")
+    assert np.array_equal(sys_.is_input, info["is_input"])
+    x = synthetic_states(1025, 4, info)
+    assert np.any(x <= 0) and np.any(x > 1)
+    want = hill_oracle.rhs(names, exprs, x, fact=hill_oracle.fAct0)
+    got = hill_oracle.interpret_programs(sys_.code_host, sys_.consts_host, sys_.off_host, sys_.len_host, x)
+    assert np.max(np.abs(got - want)) < 1e-12
+    assert np.all(got[:, sys_.is_input] == 0)
+    assert np.all(np.abs(want[:, info["deep"]] + x[:, info["deep"]]) > 1e-2)      # the 24-fold product is not negligible
+    def ops_of(g):
+        return sys_.code_host[sys_.off_host[g]: sys_.off_host[g] + sys_.len_host[g], 0].tolist()
+    assert ops_of(info["unary"]).count(OPS["NEG"]) == 2 and ops_of(info["unary"]).count(OPS["DIV"]) == 2   # unary + emits nothing
+    assert sys_.len_host[info["deep"]] == 127 and ops_of(info["deep"]).count(OPS["FACT"]) == CHAIN
+    # where no state is negative the continuation of fAct is not used: the reference's own fAct gives the same bits
+    xp = np.abs(x)
+    assert np.array_equal(hill_oracle.rhs(names, exprs, xp), hill_oracle.rhs(names, exprs, xp, fact=hill_oracle.fAct0))
+    # the row-by-row evaluation on Python floats that the trajectory references use is the same arithmetic
+    rowwise = hill_oracle.compile_rhs(names, exprs, fact=hill_oracle.fAct0)(x, rowwise=True)
+    assert np.max(np.abs(rowwise - want)) < 1e-14 and np.all(rowwise[:, sys_.is_input] == 0)
+
+
+def test_a_stack_deeper_than_the_interpreter_holds_is_rejected():
+    """MAX_STACK activations compile (the deep gene of every synthetic network), one more is a ValueError on the host"""
+    from phoenix_amd import simulator as sim
+    for L, ok in ((sim.MAX_STACK, True), (sim.MAX_STACK + 1, False)):
+        names = ["R%d" % i for i in range(L)] + ["D"]
+        edges = {(tf, "D"): {"from": tf, "weight": "1", "EC50": "0.3", "n": "2"} for tf in names[:L]}
+        exprs = ["input gene"] * L + [sim.rate_expression("D", and_chain("D", names[:L], edges), edges)]
+        assert compiled_depth(names, exprs[-1])[0] == L
+        if ok:
+            assert sim.HillSystem(names, exprs, device="cpu").len_host[L] == 127
+        else:
+            with pytest.raises(ValueError, match="deeper evaluation stack"):
+                sim.HillSystem(names, exprs, device="cpu")
