@@ -116,6 +116,8 @@ const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
     // HALF: the last hidden tile has at most 8 live rows (H <= 40 with three tiles; rho16 in phx_mfma_v3common.inc)
     const char *eh = getenv("PHX_V3_HALF");   // diagnostic: 0 = full last tile also where half of it is padding
     const bool half = p->H <= 16 * (d.HT - 1) + 8 && !(eh && eh[0] == '0');
+    const char *et = getenv("PHX_V3_TERM");   // diagnostic: 0 = no terminal tiles, every step ends with the accept pass
+    a.w.prof_level = (a.w.prof_level & 0xff) | ((et && et[0] == '0') ? FWD3_NO_TERM : 0);
     const bool split = v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1;   // small batch: the waves of a tile split its blocks
     if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
         return half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false, true>)

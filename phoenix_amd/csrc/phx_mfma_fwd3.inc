@@ -10,12 +10,19 @@
 //   * private tiles addressed through a buffer resource (scalar tile offsets, one lane offset), no masks / branches in
 //     the activations (a padding gene keeps y = 0.5, where a = l = 0, and zero weight columns);
 //   * hidden rows exchanged as 16-byte granule pairs, a tile's rows gathered in one round trip;
-//   * the accept pass (dense output at the output times, rk_common.py:168-196, interp.py) recomputes y1 from the tiles.
+//   * the accept pass (dense output at the output times, rk_common.py:168-196, interp.py) recomputes y1 from the tiles;
+//   * a TERMINAL tile -- every running trajectory's candidate step reaches its last output time, so none of them takes
+//     another step once it is accepted -- has no accept pass: its last-stage sweep holds Y0, k1, k3..k7 and y1 (the
+//     recomputed stage input) in registers and writes the dense output from them; k7, y1 and the FSAL copy, which only a
+//     further step would read, are not stored (a rejected trajectory repeats the step from untouched tiles and
+//     overwrites the rows; a failed one has them NaN-filled from out_idx).
 namespace {
 
 enum { F_Y0 = 0, F_K = 1 };
 constexpr int NVEC_FWD3 = 8;
+constexpr int FWD3_NO_TERM = 0x100;   // W1::prof_level bit (prepare_fwd3, PHX_V3_TERM=0): no tile is marked terminal
 
+// the controllers, kbs[ntg], rotf[ntg] and, in the 64 bytes behind them, termf[ntg] (ntg = NW * TPW <= 16: plan_fwd3)
 __host__ __device__ inline size_t ctlf3_bytes(int Bt, int ntg) { return ctl_bytes(Bt) + (size_t)ntg * 8 + 64; }
 
 // CALLS: the launch is d.TG independent odeint calls of d.Bcall rows under shared control (D1::Bcall, phx_solver.hpp):
@@ -53,6 +60,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     Ctl c = carve_ctl(ctlbase, Bt);
     int *kbs = reinterpret_cast<int *>(reinterpret_cast<char *>(ctlbase) + ctl_bytes(Bt));   // [ntg] ring base of the tile
     int *rotf = kbs + ntg;                                                                      // [ntg] ring turns now
+    int *termf = rotf + ntg;   // [ntg] bit 0: the tile is terminal in the step under way, bit 1: in the one that follows
     float4 *comb = reinterpret_cast<float4 *>(reinterpret_cast<char *>(ctlbase) + ((ctlf3_bytes(Bt, ntg) + 15) & ~(size_t)15));
     const int RH = ntg * F2 * 4;   // hidden rows (u, v) of one exchange; norm rows follow
     const int R = RH + ntg;
@@ -74,7 +82,8 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     };
     SegTimer tm;
     tm.start(w.prof != nullptr, c.tacc);
-    const bool prof_sweep = w.prof_level == 2;   // diagnostic: per-block timers inside the sweeps (slots 12..15)
+    const bool prof_sweep = (w.prof_level & 0xff) == 2;   // diagnostic: per-block timers inside the sweeps (slots 12..15)
+    const bool fold = !(w.prof_level & FWD3_NO_TERM);
 
     // the first tile's initial state is requested before the weights are staged (its latency flies under the staging)
     constexpr int NBX = 8;   // plan_fwd3 never gives a workgroup more gene blocks
@@ -116,7 +125,15 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
         c.accept[lb] = 0; c.fin[lb] = 0; c.out_lo[lb] = 1; c.out_hi[lb] = 1;
         c.dtf[lb] = 0.f; c.h0f[lb] = 0.f; c.dtp[lb] = 0.f; c.d1[lb] = 0.f; c.dt[lb] = 0.0;
     }
-    for (int i = tid; i < ntg; i += blockDim.x) { kbs[i] = 0; rotf[i] = 0; }
+    for (int i = tid; i < ntg; i += blockDim.x) { kbs[i] = 0; rotf[i] = 0; termf[i] = 0; }
+    // Terminal tiles (bit `bit` of termf): at least one trajectory of the tile runs and the candidate step of every
+    // running one reaches its last output time -- `reach`, the controller's own comparison with t[T - 1].  Called by
+    // whole waves where dt becomes known, thread lb with its trajectory's flags; a barrier that follows publishes it.
+    auto mark_terminal = [&](int bit, bool run, bool reach) {
+        const unsigned long long seg = 0xffffull << (lane & 48);   // the wave's lanes of this trajectory tile
+        const unsigned long long mrun = __ballot(run) & seg, mshort = __ballot(run && !reach) & seg;
+        if (tid < Bt && li == 0) termf[tid >> 4] = (termf[tid >> 4] & ~(1 << bit)) | ((fold && mrun && !mshort) ? 1 << bit : 0);
+    };
     // ---- initial state: Y0 tiles <- y0, sol[0] <- y0
     {
         const int ttl = wtile, b = rowof(ttl * 16 + li);
@@ -308,6 +325,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
         constexpr int RM = decltype(RMc)::value;
         constexpr bool STK = DO2 && RM != 2;
         constexpr bool SK1 = DO2 && !DO1 && NK == 6;   // last stage: beta_72 = c_err2 = 0, k_2 is not read
+        constexpr bool FOLD = SK1 && RM == 3;          // ... of a step: a terminal tile takes the TERM bodies
         constexpr int NKL = NK > 0 ? NK : 1;
         tm.mark(0);
         // opaque copies: keeps the derived LDS / tile addresses of every sweep variant from being hoisted to the kernel top
@@ -321,6 +339,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const int lb = ttl * 16 + li;
             const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
+            const bool term = FOLD && (__builtin_amdgcn_readfirstlane(termf[ttl]) & 1);
             float ty0[8], tk[NKL][8];
             auto issue = [&](int bl) {
                 bload8(trs, lane32, toff(F_Y0, ttl, bl), ty0);
@@ -393,8 +412,20 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
 #pragma unroll
             for (int f = 0; f < F2; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
             float r0 = 0.f, r1 = 0.f;
-            auto body = [&](auto LASTc, int bl) {
+            // a terminal tile's running trajectories (TERM bodies): the step and the output rows it would finish with
+            bool live = false;
+            int oi = T;
+            double t0d = 0.0, t1d = 1.0, sgd = 1.0;
+            TimeRow tb{t, false};
+            if (term) {
+                live = b < B && !c.done[lb];
+                oi = c.out_idx[lb];
+                t0d = c.rk_t1[lb]; t1d = t0d + c.dt[lb]; sgd = (double)sg;
+                tb = trowT(t, T, cfg, shared ? trow_sh : min(b, B - 1));
+            }
+            auto body = [&](auto LASTc, auto TERMc, int bl) {
                 constexpr bool LAST = decltype(LASTc)::value != 0;
+                constexpr bool TERM = decltype(TERMc)::value != 0;   // only with FOLD: dense output instead of the k_7 store
                 const float *Wb = lds + (long long)bl * BLKF;
                 const float *rg = Wb + RGOFF;
                 float rr[8];
@@ -434,9 +465,20 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                 }
 #pragma unroll
                 for (int j = 0; j < 8; ++j) y0c[j] = ty0[j];
-                if (RM == 2) {
+                if (RM == 2 || TERM) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) k0c[j] = tk[0][j];
+                }
+                float ym[8];
+                if constexpr (TERM) {   // the dense output's midpoint combination as accept_pass forms it; k_7's term follows
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) ym[j] = tk[0][j] * (dtl * DP_CMID[0]);
+#pragma unroll
+                    for (int kk = 1; kk < 6; ++kk) {
+                        const float cf = dtl * DP_CMID[kk];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) ym[j] += tk[kk][j] * cf;
+                    }
                 }
                 // ---- 2. the tile registers are free: request the next block's tiles (fenced: see k1_solve_adj3)
                 __builtin_amdgcn_sched_barrier(0);
@@ -468,7 +510,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                     }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) kv[j] = sg * (rr[j] * (jv[j] - ysI[j]));
-                    if (STK) bstore8(trs, lane32, toff(F_K + ring(kb, NK), ttl, bl), kv);
+                    if (STK && !TERM) bstore8(trs, lane32, toff(F_K + ring(kb, NK), ttl, bl), kv);
                     if (RM != 0) {
                         if (RM == 3) {
 #pragma unroll
@@ -490,6 +532,21 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                                 const float tol = cfg.atol + cfg.rtol * fmaxf(fabsf(y0c[j]), fabsf(ysI[j]));
                                 const float q0 = ey[j] / tol;
                                 r0 += q0 * q0;
+                            }
+                        }
+                    }
+                    if constexpr (TERM) {   // accept_pass's rows out_idx .. T - 1 from registers: y1 is this stage's input
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) ym[j] += kv[j] * (dtl * DP_CMID[6]);
+                        if (live) {
+                            for (int jo = oi; jo < T; ++jo) {
+                                const double xx = (sgd * tb[jo] - t0d) / (t1d - t0d);
+                                const InterpX ix = make_interp_x(xx);
+                                float ov[8];
+#pragma unroll
+                                for (int j = 0; j < 8; ++j)
+                                    ov[j] = interp_eval(y0c[j], ysI[j], y0c[j] + ym[j], k0c[j], kv[j], dtl, ix);
+                                row_store8(sol, (long long)jo * d.BN + (long long)b * N, (blk0 + bl) * 32 + gmap(lq, 0), N, true, ov);
                             }
                         }
                     }
@@ -522,9 +579,14 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                 if (tm.on && prof_sweep && DO1) tm.mark(15);   // diagnostic: next input + activations + P1
 #endif
             };
-            if (has_blocks) {
-                for (int bl = b_lo; bl + 1 < b_hi; ++bl) body(I3<0>{}, bl);
-                body(I3<1>{}, b_hi - 1);
+            if (FOLD && term) {   // (wave uniform; a second instantiation of the block loop, no branch inside the bodies)
+                if (has_blocks) {
+                    for (int bl = b_lo; bl + 1 < b_hi; ++bl) body(I3<0>{}, I3<FOLD ? 1 : 0>{}, bl);
+                    body(I3<1>{}, I3<FOLD ? 1 : 0>{}, b_hi - 1);
+                }
+            } else if (has_blocks) {
+                for (int bl = b_lo; bl + 1 < b_hi; ++bl) body(I3<0>{}, I3<0>{}, bl);
+                body(I3<1>{}, I3<0>{}, b_hi - 1);
             }
             if (SPLIT) {   // the tile's waves add their partial rows / norm partials in LDS, part 0 publishes
                 float4 *mine = comb + (long long)wv * (F2 + 1) * 64 + lane;
@@ -575,8 +637,10 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
             const bool rot = __builtin_amdgcn_readfirstlane(rotf[ttl]) != 0;
+            if (__builtin_amdgcn_readfirstlane(termf[ttl]) & 1) continue;   // terminal: the last-stage sweep wrote its rows
             const bool adv = !c.done[lb] && c.accept[lb];
             if (!__any(adv)) continue;
+            const bool keep = adv && !c.fin[lb];   // the trajectory takes another step: only then is its state read again
             const int lo = c.out_lo[lb], hi = c.out_hi[lb];
             const double t0 = c.rk_t0[lb], t1 = c.rk_t1[lb];
             const float dts = c.dtp[lb];
@@ -631,7 +695,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                         }
                     }
                 }
-                if (adv) {   // per-lane select: rejected / finished trajectories keep their state
+                if (keep) {   // per-lane select: rejected / finished trajectories keep their state
                     bstore8(trs, lane32, toff(F_Y0, ttl, bl), y1v);
                     if (!rot) bstore8(trs, lane32, toff(F_K + kb, ttl, bl), k[6]);   // FSAL by copy (mixed decisions)
                 }
@@ -676,6 +740,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             sweep(I3<1>{}, I3<1>{}, I3<0>{}, I3<2>{}, 1, tH, 0u, tN);
             norms(1, nv);
         }
+        bool run = false, reach = false;
         if (tid < Bt && !c.done[tid]) {
             const float h0 = c.h0f[tid];
             const float d2 = nv[0] / h0;
@@ -683,7 +748,13 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             c.dt[tid] = dt; c.dtf[tid] = (float)dt; c.nfe[tid] = 2;
             const double t0 = c.rk_t1[tid];
             if (!(t0 + dt > t0)) { c.st[tid] = PHX_ERR_DT_UNDERFLOW; c.done[tid] = 1; }
+            else {
+                const TimeRow tb = trowT(t, T, cfg, shared ? trow_sh : rowof(tid));
+                run = true;
+                reach = (double)c.sgn[tid] * tb[T - 1] <= t0 + dt;
+            }
         }
+        mark_terminal(0, run, reach);
         int active = count_active();
         while (active > 0 && !x.aborted) {
             unsigned int tH = ++x.tag;
@@ -701,6 +772,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             }
             norms(1, nv);
             // ---- controller (rk_common.py:150-220)
+            bool run = false, reach = false;   // of the step that follows (mark_terminal)
             if (tid < Bt && !c.done[tid]) {
                 const int lb = tid;
                 const int b = rowof(lb);
@@ -737,9 +809,11 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                     const double tn = c.rk_t1[lb];
                     if ((long long)nsi >= cfg.max_steps) { c.st[lb] = PHX_ERR_MAX_STEPS; dn = 1; }
                     else if (!(tn + dtn > tn)) { c.st[lb] = PHX_ERR_DT_UNDERFLOW; dn = 1; }
+                    else { run = true; reach = sg * tb[T - 1] <= tn + dtn; }
                 }
                 c.fin[lb] = dn;
             }
+            mark_terminal(1, run, reach);
             __syncthreads();
             // the ring of a tile turns (k_7 -> k_1 without a copy) when every trajectory of it either continues with an
             // accepted step or is out after this step
@@ -759,6 +833,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             accept_pass();
             __syncthreads();
             if (tid < ntg && rotf[tid]) kbs[tid] = ring(kbs[tid], 6);
+            if (tid < ntg) termf[tid] >>= 1;   // the step that follows is now the step under way
             if (tid < Bt && !c.done[tid] && c.fin[tid]) c.done[tid] = 1;
             active = count_active();
         }

@@ -61,7 +61,8 @@ struct W1 {
     const float *wimg;         // chunked hidden layer: pre-packed LDS images [gene block][chunk][blk_floats_ch]
     float *hq;                 // k1_solve_adj2: wave-private transposed hidden rows [WG][8][TPW][7][2HT][64] float4
     unsigned long long *part1, *zbuf1;   // third-generation kernels: the second set of exchange buffers (xset_begin)
-    int prof_level;            // k1_solve_fwd3: PHX_PROF level (2: per-block timers inside the sweeps)
+    int prof_level;            // k1_solve_fwd3: PHX_PROF level (2: per-block timers inside the sweeps) in the low byte,
+                               // above it the diagnostic switches of that kernel (FWD3_NO_TERM, phx_mfma_fwd3.inc)
 };
 
 }  // namespace phxt
