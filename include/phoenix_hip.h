@@ -410,6 +410,34 @@ int phx_effects_neighbors(const phx_params *p, int mode, const float *y, const f
                           float tau, const unsigned char *regulator_ok, const unsigned char *target_ok, int *gene, float *value,
                           unsigned *count, float *strength, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Pathway permutation tests on one score per gene (the reference's create_permutation_test_files_aws.R, whose 500 draws per
+ * pathway this call replaces).  scores [N] float; the P pathways in CSR form: ptr [P + 1] (ptr[0] = 0, non-decreasing,
+ * ptr[P] = nnz) and idx [nnz], the member genes of pathway p at [ptr[p], ptr[p + 1]), each inside [0, N) and unique within
+ * its pathway -- the caller vouches for ptr and idx, they are on the device and are not checked.  Permutation number r in
+ * [first, first + n_perm) is defined by (seed, r) alone, in arithmetic modulo 2^64:
+ *   c = r << 14 | g                                          for gene g < N <= 16384, r < 2^50
+ *   mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31
+ *   key[g] = (mix(mix(seed + 0x9E3779B97F4A7C15 * (c + 1))) & ~0x3FFF) | g        (the low 14 bits make keys distinct)
+ *   order_r = the genes by ascending key;  permuted_r[g] = scores[order_r[g]];  x_r[p] = sum of permuted_r over pathway p
+ * Every pathway sees the same permutation r (the reference draws one per pathway and replicate; each pathway's null
+ * distribution is the same either way).  The sums are double, in an order that depends on the pathway's member list alone.
+ *   base  [P]   that sum over `scores` themselves, in the same order
+ *   count [P]   #{r : base < x_r}, strict as the reference's mean(base_res < all_perm_results)
+ *   s1, s2 [P]  sum_r (x_r - base) and sum_r (x_r - base)^2: shifted by base so that the variance does not cancel
+ * phx_pathways.hip: min(n_perm, 512) workgroups take the permutations round-robin; one permutation is 8-byte keys sorted
+ * in LDS (a bitonic network over the next power of two, 128 KiB at N = 16384) and then the permuted scores in the same LDS;
+ * 16 lanes walk a pathway's members, read as 16-bit words; a second kernel adds the workgroups' partials in order.  No
+ * atomics: base and count are exact, s1 and s2 are sums whose order is fixed by (first, n_perm) -- never by the device -- so
+ * identical calls give identical bits, and a range split by `first` over calls or devices gives the same counts.
+ * Nothing allocates or synchronises.  PHX_ERR_BAD_ARG before any device call: N < 1, N > 16384, P < 1, nnz < 0, n_perm < 1,
+ * first < 0, first + n_perm > 2^50, a null scores / ptr / result, a null idx with nnz > 0.  PHX_ERR_WORKSPACE when workspace
+ * is null or workspace_bytes < phx_pathway_permutations_workspace_bytes(N, P, nnz, n_perm) (0 for arguments the call
+ * refuses): the narrowed member list and 24 bytes per workgroup and pathway. */
+size_t phx_pathway_permutations_workspace_bytes(int N, int P, long long nnz, long long n_perm);
+int phx_pathway_permutations(const float *scores, int N, const long long *ptr, const int *idx, int P, long long nnz,
+                             unsigned long long seed, long long first, long long n_perm, double *base, long long *count,
+                             double *s1, double *s2, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

@@ -38,7 +38,8 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
            "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges",
            "phx_effects_rank_workspace_bytes", "phx_effects_gather", "phx_effects_rank_counts",
-           "phx_effects_neighbors_workspace_bytes", "phx_effects_neighbors")
+           "phx_effects_neighbors_workspace_bytes", "phx_effects_neighbors", "phx_pathway_permutations_workspace_bytes",
+           "phx_pathway_permutations")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -48,6 +49,8 @@ EDGES_ORIENT, EDGES_DIAGONAL = 1, 2                          # phx_edges_flags
 EDGES_COUNT, EDGES_EMIT = 0, 1                               # phx_edges_pass
 NEIGHBORS_AXES = {"regulator": 0, "target": 1}                # phx_neighbors_axis
 NEIGHBORS_MAX_K = 64
+PATHWAYS_MAX_N = 16384                                       # phx_pathway_permutations: a gene is 14 bits of its sort key
+PATHWAYS_MAX_R = 1 << 50                                     # ... and first + n_perm stays below this
 EDGES_BINS = 4096                                            # workspace: uint32 hist[EDGES_BINS], then uint32 count
 STATUS_TEXT = {
     1: "max_num_steps exceeded",
@@ -144,6 +147,10 @@ def load():
     lib.phx_effects_neighbors_workspace_bytes.restype = C.c_size_t
     lib.phx_effects_neighbors.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 4 + \
         [C.c_float, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.phx_pathway_permutations_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_longlong]
+    lib.phx_pathway_permutations_workspace_bytes.restype = C.c_size_t
+    lib.phx_pathway_permutations.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_longlong, C.c_ulonglong, C.c_longlong,
+                                             C.c_longlong, vp, vp, vp, vp, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

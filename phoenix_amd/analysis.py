@@ -326,3 +326,198 @@ def network_score(odenet, regulator, target, orient=False, diagonal=False, y=Non
     with torch.no_grad():
         p, mode, y2, ph, r, t = _network_call("network_score", odenet, regulator, target, y, reduce)
         return NetworkScore(*engine.network_score(p, mode, r, t, y=y2, ph=ph, orient=orient, diagonal=diagonal))
+
+
+# ------------------------------------------------------------------ pathway permutation tests
+def consolidate_gene_scores(gene_names, scores):
+    """One score per gene symbol from one score per array entry (create_permutation_test_files_aws.R:68-84).  An entry
+    whose name holds "///" names several genes: it is split, the parts are trimmed, every part inherits the entry's
+    score, and a (part, score) pair that repeats within the entry is dropped.  A name that then occurs more than once
+    gets the mean of its scores.  The order is the first appearance among the single-name entries followed by the split
+    ones, as the script's `rbind` leaves them.  Returns (names: list of str, scores: float64 numpy array)."""
+    gene_names = [str(n) for n in gene_names]
+    scores = np.asarray(scores.detach().cpu() if isinstance(scores, torch.Tensor) else scores, dtype=np.float64).reshape(-1)
+    if len(gene_names) != scores.shape[0]:
+        raise ValueError("consolidate_gene_scores: %d names for %d scores" % (len(gene_names), scores.shape[0]))
+    rows = [(n, s) for n, s in zip(gene_names, scores.tolist()) if "///" not in n]
+    seen = set()
+    for n, s in zip(gene_names, scores.tolist()):
+        if "///" in n:
+            for part in n.split("///"):
+                part = part.strip()
+                if (n, part, s) not in seen:
+                    seen.add((n, part, s))
+                    rows.append((part, s))
+    groups = {}
+    for n, s in rows:
+        groups.setdefault(n, []).append(s)
+    names = list(groups)
+    return names, np.array([sum(groups[n]) / len(groups[n]) for n in names], dtype=np.float64)
+
+
+Pathways = collections.namedtuple("Pathways", ("names", "ptr", "idx", "kept"))
+
+
+def read_pathways(fp, gene_names):
+    """Host parser of the reference's wide pathway table (<analysis>_pathway_binary_wide.csv): a header row with a
+    `pathway` column and one column per gene, then one row of 0 / 1 per pathway; of a pathway that occurs again the first
+    row counts.  The genes of `gene_names` (unique names, e.g. from `consolidate_gene_scores`) that are columns of the
+    table are kept, in the order of `gene_names` (create_permutation_test_files_aws.R:90-100): the test permutes the
+    scores of these genes only.  Returns Pathways(names, ptr, idx, kept): the pathway names in file order, the members
+    in CSR form (`ptr` int64 [P + 1], `idx` int32 [nnz], ascending positions in the kept genes) and `kept` int64, the
+    kept genes as indices into `gene_names` -- `scores[kept]` are the scores the members index."""
+    import csv
+    gene_names = [str(n) for n in gene_names]
+    if len(set(gene_names)) != len(gene_names):
+        raise ValueError("read_pathways: gene_names must be unique (consolidate_gene_scores makes them so)")
+    f = fp if hasattr(fp, "read") else open(fp, newline="")
+    try:
+        rows = csv.reader(f)
+        header = next(rows, None)
+        if header is None or "pathway" not in header:
+            raise ValueError("read_pathways: the table has no `pathway` column")
+        column = {}
+        for c, name in enumerate(header):
+            column.setdefault(name, c)
+        pcol = column.pop("pathway")
+        kept = [k for k, n in enumerate(gene_names) if n in column]
+        cols = [column[gene_names[k]] for k in kept]
+        names, members, known = [], [], set()
+        for row in rows:
+            if not row or row[pcol] in known:
+                continue
+            known.add(row[pcol])
+            names.append(row[pcol])
+            members.append(np.nonzero(np.array([float(row[c]) for c in cols], dtype=np.float64))[0].astype(np.int32))
+    finally:
+        if f is not fp:
+            f.close()
+    ptr = np.zeros(len(names) + 1, dtype=np.int64)
+    np.cumsum([len(m) for m in members], out=ptr[1:])
+    idx = np.concatenate(members).astype(np.int32) if members else np.zeros(0, np.int32)
+    return Pathways(names, ptr, idx, np.array(kept, dtype=np.int64))
+
+
+def _host_array(x):
+    return np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+
+
+def check_pathways(name, ptr, idx, N):
+    """the ValueErrors of a CSR pathway list on the host, before a device is needed: (ptr int64, idx int64) as numpy"""
+    ptr, idx = np.asarray(ptr), np.asarray(idx)
+    if ptr.ndim != 1 or idx.ndim != 1 or ptr.dtype.kind not in "iu" or (idx.size and idx.dtype.kind not in "iu"):
+        raise ValueError("%s: ptr and idx must be one-dimensional integer arrays" % name)
+    ptr, idx = ptr.astype(np.int64), idx.astype(np.int64)
+    if ptr.shape[0] < 2:
+        raise ValueError("%s: at least one pathway is needed (ptr has P + 1 entries)" % name)
+    if ptr[0] != 0 or ptr[-1] != idx.shape[0] or np.any(np.diff(ptr) < 0):
+        raise ValueError("%s: ptr must start at 0, not decrease and end at len(idx) = %d" % (name, idx.shape[0]))
+    if idx.size and (idx.min() < 0 or idx.max() >= N):
+        raise ValueError("%s: idx must lie in [0, %d), got %d .. %d" % (name, N, idx.min(), idx.max()))
+    owner = np.repeat(np.arange(ptr.shape[0] - 1, dtype=np.int64), np.diff(ptr))
+    if np.unique(owner * N + idx).shape[0] != idx.shape[0]:
+        raise ValueError("%s: a pathway lists a gene more than once" % name)
+    return ptr, idx
+
+
+class PermutationTest:
+    """The result of `pathway_permutation_test`: the raw sums of the permutations [first, first + n_perm) of `seed` --
+    `base` float64 [P], `count` int64 [P], `s1`, `s2` float64 [P] (include/phoenix_hip.h: phx_pathway_permutations), on
+    the device -- and, as properties computed from them in float64, the columns of the reference's output file with
+    R = n_perm: `mean` = base + s1 / R, `sd` = sqrt(max(0, (s2 - s1^2 / R) / (R - 1))), `z` = (base - mean) / sd where
+    sd > 0 and 0 elsewhere, `p` = count / R."""
+
+    def __init__(self, base, count, s1, s2, n_perm, first, seed):
+        self.base, self.count, self.s1, self.s2 = base, count, s1, s2
+        self.n_perm, self.first, self.seed = int(n_perm), int(first), int(seed)
+
+    @property
+    def mean(self):
+        return self.base + self.s1 / self.n_perm
+
+    @property
+    def sd(self):
+        if self.n_perm < 2:
+            raise ValueError("PermutationTest: a standard deviation needs at least 2 permutations")
+        R = self.n_perm
+        return torch.sqrt(torch.clamp((self.s2 - self.s1 * self.s1 / R) / (R - 1), min=0.0))
+
+    @property
+    def z(self):
+        sd = self.sd
+        live = sd > 0
+        return torch.where(live, (self.base - self.mean) / torch.where(live, sd, torch.ones_like(sd)), torch.zeros_like(sd))
+
+    @property
+    def p(self):
+        return self.count.to(torch.float64) / self.n_perm
+
+    @staticmethod
+    def merge(a, b):
+        """The result over both ranges of two results of one seed on the same scores and pathways whose permutation
+        ranges are adjacent (one ends where the other starts): how a run is extended, and how shards of the permutations
+        (`parallel.shard_range`) are combined.  `b` is moved to `a`'s device."""
+        if a.seed != b.seed:
+            raise ValueError("PermutationTest.merge: different seeds (%d, %d)" % (a.seed, b.seed))
+        if b.first < a.first:
+            a, b = b, a
+        if a.first + a.n_perm != b.first:
+            raise ValueError("PermutationTest.merge: the ranges [%d, %d) and [%d, %d) are not adjacent and disjoint"
+                             % (a.first, a.first + a.n_perm, b.first, b.first + b.n_perm))
+        dev = a.base.device
+        if a.base.shape != b.base.shape or not torch.equal(a.base, b.base.to(dev)):
+            raise ValueError("PermutationTest.merge: the two results are not of the same scores and pathways")
+        return PermutationTest(a.base, a.count + b.count.to(dev), a.s1 + b.s1.to(dev), a.s2 + b.s2.to(dev),
+                               a.n_perm + b.n_perm, a.first, a.seed)
+
+
+def pathway_permutation_test(scores, pathways, n_perm=500, seed=0, first=0, device="cuda"):
+    """The permutation test of create_permutation_test_files_aws.R on the device: for every pathway, the sum of its genes'
+    scores against the same sum under `n_perm` permutations of the gene labels.  `scores`: one score per kept gene
+    (`scores[pathways.kept]` of the consolidated scores), finite; `pathways`: a `Pathways`, or any (names, ptr, idx, ...)
+    with the members in CSR form.  At most 16384 genes.  Returns a `PermutationTest` on `device`.
+    The permutations are numbered: number r of `seed` is the same on every device and in every call, and this call takes
+    [first, first + n_perm), so a run is extended or sharded by `first` and joined with `PermutationTest.merge`.  All
+    pathways see the same permutation r; the reference draws a fresh one per pathway and replicate.  The null distribution of
+    every single pathway is the same either way, only the dependence between the statistics of different pathways differs.
+    first + n_perm >= 2 (a standard deviation needs two draws)."""
+    name = "pathway_permutation_test"
+    seed, first, n_perm = engine.check_permutation_range(name, seed, first, n_perm)
+    if first + n_perm < 2:
+        raise ValueError("%s: first + n_perm must be at least 2, got %d + %d" % (name, first, n_perm))
+    s = scores.detach() if isinstance(scores, torch.Tensor) else _host_array(scores).astype(np.float32)
+    if s.ndim != 1 or not 1 <= s.shape[0] <= 16384:
+        raise ValueError("%s: scores must be [N] with 1 <= N <= 16384, got %s" % (name, tuple(s.shape)))
+    ptr, idx = check_pathways(name, _host_array(pathways[1]), _host_array(pathways[2]), s.shape[0])
+    if not isinstance(s, torch.Tensor):
+        s = torch.from_numpy(np.ascontiguousarray(s))
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError("%s: scores must be finite" % name)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("phoenix_amd: %s runs on the GPU (cuda/HIP device) only, got device %r" % (name, str(device)))
+    with torch.no_grad(), torch.cuda.device(device):
+        s = s.to(device=device, dtype=torch.float32)
+        out = engine.pathway_permutations(s, torch.from_numpy(ptr).to(device), torch.from_numpy(idx.astype(np.int32)).to(device),
+                                          seed, first, n_perm)
+    return PermutationTest(*out, n_perm=n_perm, first=first, seed=seed)
+
+
+def write_permutation_table(fp, result, pathway_names):
+    """Writes the reference's output file (create_permutation_test_files_aws.R:114-116, `write.csv(..., row.names = F)`):
+    the header "pathway","phnx_z_score","mean_path_score","sd_path_score","phnx_p_val", then one row per pathway sorted
+    by z descending (stably: equal z keep the order of `pathway_names`), the name quoted, the numbers as %.15g.  `fp`: a
+    path or an open text file.  Returns the number of rows."""
+    names = [str(n) for n in pathway_names]
+    cols = [np.asarray(x.detach().cpu(), dtype=np.float64) for x in (result.z, result.mean, result.sd, result.p)]
+    if any(c.shape != (len(names),) for c in cols):
+        raise ValueError("write_permutation_table: %d names for %d pathways" % (len(names), cols[0].shape[0]))
+    lines = ['"pathway","phnx_z_score","mean_path_score","sd_path_score","phnx_p_val"\n']
+    for k in np.argsort(-cols[0], kind="stable").tolist():
+        lines.append('"%s",%.15g,%.15g,%.15g,%.15g\n' % ((names[k].replace('"', '""'),) + tuple(float(c[k]) for c in cols)))
+    if hasattr(fp, "write"):
+        fp.write("".join(lines))
+    else:
+        with open(fp, "w") as f:
+            f.write("".join(lines))
+    return len(names)

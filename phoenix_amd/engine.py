@@ -914,8 +914,85 @@ def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=
     return gene.to(torch.int64), value, count.to(torch.int64), strength
 
 
+OP_PATHWAYS = 10     # workspace-cache key of pathway_permutations (phx_pathway_permutations_workspace_bytes sizes it)
+
+
+def check_permutation_range(name, seed, first, n_perm):
+    """the ValueErrors of (seed, first, n_perm) of `pathway_permutations`, raised before a device is needed"""
+    if not _is_int(seed) or not 0 <= seed < 2 ** 64:
+        raise ValueError("%s: seed must be an integer in [0, 2^64), got %r" % (name, seed))
+    if not _is_int(first) or first < 0:
+        raise ValueError("%s: first must be an integer >= 0, got %r" % (name, first))
+    if not _is_int(n_perm) or n_perm < 1:
+        raise ValueError("%s: n_perm must be an integer >= 1, got %r" % (name, n_perm))
+    if first + n_perm > _lib.PATHWAYS_MAX_R:
+        raise ValueError("%s: first + n_perm must not exceed 2^50, got %d + %d" % (name, first, n_perm))
+    return int(seed), int(first), int(n_perm)
+
+
+def pathway_permutations(scores, ptr, idx, seed, first, n_perm):
+    """phx_pathway_permutations (include/phoenix_hip.h): `scores` float32 [N], N <= 16384, and the P pathways in CSR form,
+    `ptr` int64 [P + 1] and `idx` int32 or int64 [nnz] (member genes, unique within a pathway), all on one device.  Returns
+    the raw results of the permutations [first, first + n_perm) of `seed` on that device: (base float64 [P], count int64
+    [P], s1 float64 [P], s2 float64 [P]).  ValueError for anything the kernel would trust: a `ptr` that is not a CSR
+    pointer of `idx`, a member outside [0, N) or repeated in its pathway, a score that is not finite.  The pathways go to
+    the kernel sorted by size (the lanes of a wave then walk lists of similar length) and the results come back in the
+    caller's order; a pathway's own member order, which fixes the order of its sums, is kept."""
+    name = "pathway_permutations"
+    seed, first, n_perm = check_permutation_range(name, seed, first, n_perm)
+    for what, x in (("scores", scores), ("ptr", ptr), ("idx", idx)):
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("%s: `%s` must be a tensor on the GPU, got %s" % (name, what, type(x).__name__))
+        _require_gpu(x, what)
+    dev = scores.device
+    if ptr.device != dev or idx.device != dev:
+        raise ValueError("%s: scores, ptr and idx must be on one device" % name)
+    if scores.dim() != 1 or not 1 <= scores.shape[0] <= _lib.PATHWAYS_MAX_N:
+        raise ValueError("%s: scores must be [N] with 1 <= N <= %d, got %s" % (name, _lib.PATHWAYS_MAX_N, tuple(scores.shape)))
+    if ptr.dim() != 1 or ptr.dtype != torch.int64 or ptr.shape[0] < 2:
+        raise ValueError("%s: ptr must be int64 [P + 1] with P >= 1, got %s %s" % (name, ptr.dtype, tuple(ptr.shape)))
+    if idx.dim() != 1 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s: idx must be int32 or int64 [nnz], got %s %s" % (name, idx.dtype, tuple(idx.shape)))
+    N, P, nnz = scores.shape[0], ptr.shape[0] - 1, idx.shape[0]
+    if P >= 2 ** 31:
+        raise ValueError("%s: at most 2^31 - 1 pathways, got %d" % (name, P))
+    scores, ptr, idx = scores.detach().contiguous(), ptr.contiguous(), idx.contiguous()
+    sizes = ptr[1:] - ptr[:-1]
+    if int(ptr[0]) != 0 or int(ptr[-1]) != nnz or (P and int(sizes.min()) < 0):
+        raise ValueError("%s: ptr must start at 0, not decrease and end at len(idx) = %d" % (name, nnz))
+    if nnz and (int(idx.min()) < 0 or int(idx.max()) >= N):
+        raise ValueError("%s: idx must lie in [0, %d), got %d .. %d" % (name, N, int(idx.min()), int(idx.max())))
+    owner = torch.repeat_interleave(torch.arange(P, device=dev), sizes)
+    if nnz and int(torch.unique(owner * N + idx).numel()) != nnz:
+        raise ValueError("%s: a pathway lists a gene more than once" % name)
+    if not bool(torch.isfinite(scores).all()):
+        raise ValueError("%s: scores must be finite" % name)
+    # by size, largest first, stably: the pathways move as blocks, their members stay in order
+    order = torch.sort(sizes, descending=True, stable=True).indices
+    s_sizes = sizes[order]
+    s_ptr = torch.zeros(P + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(s_sizes, 0, out=s_ptr[1:])
+    within = torch.arange(nnz, device=dev) - torch.repeat_interleave(s_ptr[:-1], s_sizes)
+    s_idx = idx[torch.repeat_interleave(ptr[:-1][order], s_sizes) + within].to(torch.int32)
+    lib = _lib.load()
+    nbytes = lib.phx_pathway_permutations_workspace_bytes(N, P, nnz, n_perm)
+    wkey = (dev.index, _stream_raw(dev.index), OP_PATHWAYS)
+    ws = _ws_cache.get(wkey)
+    if ws is None or ws.numel() < nbytes:
+        ws = _ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    base = torch.empty(P, dtype=torch.float64, device=dev)
+    count = torch.empty(P, dtype=torch.int64, device=dev)
+    s1 = torch.empty(P, dtype=torch.float64, device=dev)
+    s2 = torch.empty(P, dtype=torch.float64, device=dev)
+    _check_call(lib.phx_pathway_permutations(_p(scores), N, _p(s_ptr), _p(s_idx), P, nnz, seed, first, n_perm, _p(base), _p(count),
+                                             _p(s1), _p(s2), _p(ws), nbytes, _stream_ptr()))
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(P, device=dev)
+    return base[inverse], count[inverse], s1[inverse], s2[inverse]
+
+
 OP_NETSCORE = 8      # workspace-cache key of network_score (phx_effects_rank_workspace_bytes sizes it)
-NETSCORE_TILE = 64   # the tile by which phx_effects_gather wants its keys grouped
+NETSCORE_TILE = 64  # the tile by which phx_effects_gather wants its keys grouped
 
 
 def _netscore_states(name, params, mode, y, ph):
