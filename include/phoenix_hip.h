@@ -278,6 +278,29 @@ int phx_hill_rhs(const int *code, const int *off, const int *len, const float *c
 int phx_hill_simulate(const int *code, const int *off, const int *len, const float *consts, const float *x0,
                       const double *times, int T, double dt_max, float *out, int B, int N, void *stream);
 
+/* The true Jacobian of those rate expressions, the simulator's side of the reference's Jacobian comparators (SURVEY.md row
+ * 21: dynamo_extract_matrix.py, helper_true_velo.py).  The programs are those of phx_hill_rhs; the sparse pattern comes in
+ * CSR form by target: eptr [N + 1] (eptr[0] = 0, eptr[N] = E, not decreasing) and ereg [E], the regulators of target j in
+ * ereg[eptr[j] .. eptr[j + 1]) (the caller lists the distinct PUSHX genes of program j; the call trusts eptr and only
+ * compares ereg).  With J[b, e] = d rate_target(e) / d x_ereg[e] at x[b], x [B, N]:
+ *     mode 0   out [B, E] = J             mode 1   out [E] = mean over b of J[b, e]        mode 2   out [E] = mean of |J[b, e]|
+ * One thread per entry interprets the target's program forward-mode on (value, derivative) pairs in fp32: the value half
+ * is phx_hill_rhs's, operation by operation; PUSHC has derivative 0, PUSHX g has (g == ereg[e]), ADD / SUB / NEG are linear,
+ * MUL gives l' r + l r', DIV with q = l / r gives (l' - q r') / r, FACT(B, K_n, n) on (tf, tf') gives
+ * B K_n n tf^(n-1) / (K_n + tf^n)^2 tf' for tf > 0 and 0 for tf <= 0, where phx_hill_rhs continues fAct by 0.  An ereg[e]
+ * that program never pushes gives exactly +0.  Modes 1 and 2 sum in fp64 -- the rows in min(1024, ceil(B / 32)) contiguous
+ * chunks, ascending within a chunk, then the chunks in order -- divide by B and round once to fp32: the order depends on B
+ * alone, nothing is atomic, two calls agree bit for bit.  Rows and entries are strided over capped grid dimensions: B, N
+ * and E are bounded by their types only, and no array is sized by a gene's number of regulators.
+ * PHX_ERR_BAD_ARG before any device call: a null code / off / len / consts / eptr / ereg / x / out, B < 1, N < 1, E < 0, a
+ * mode outside 0 .. 2.  E == 0: PHX_OK, nothing is launched.  PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_hill_jacobian_workspace_bytes(B, N, E, mode): the chunk sums, [chunks][E] doubles, and 0 where none are needed (mode
+ * 0, B <= 32, or arguments the call refuses).  Nothing allocates or synchronises. */
+size_t phx_hill_jacobian_workspace_bytes(int B, int N, long long E, int mode);
+int phx_hill_jacobian(const int *code, const int *off, const int *len, const float *consts, const long long *eptr,
+                      const int *ereg, const float *x, int B, int N, long long E, int mode, float *out, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* the scoring tail of the gene-influence scan (find_gene_influences.py:64-77) on the solver's
  * own output.  sol [T, 2 * pairs * B, N] is the block phx_odeint wrote for 2 * pairs calls of B rows (opts->calls): call
  * 2j is the unperturbed solve of pair j, call 2j + 1 the perturbed one; genes_host [pairs] (HOST) names the perturbed

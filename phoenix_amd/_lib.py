@@ -39,7 +39,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges",
            "phx_effects_rank_workspace_bytes", "phx_effects_gather", "phx_effects_rank_counts",
            "phx_effects_neighbors_workspace_bytes", "phx_effects_neighbors", "phx_pathway_permutations_workspace_bytes",
-           "phx_pathway_permutations")
+           "phx_pathway_permutations", "phx_hill_jacobian_workspace_bytes", "phx_hill_jacobian")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -151,6 +151,9 @@ def load():
     lib.phx_pathway_permutations_workspace_bytes.restype = C.c_size_t
     lib.phx_pathway_permutations.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_longlong, C.c_ulonglong, C.c_longlong,
                                              C.c_longlong, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.phx_hill_jacobian_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_int]
+    lib.phx_hill_jacobian_workspace_bytes.restype = C.c_size_t
+    lib.phx_hill_jacobian.argtypes = [vp] * 7 + [C.c_int, C.c_int, C.c_longlong, C.c_int, vp, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

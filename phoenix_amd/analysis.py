@@ -328,6 +328,72 @@ def network_score(odenet, regulator, target, orient=False, diagonal=False, y=Non
         return NetworkScore(*engine.network_score(p, mode, r, t, y=y2, ph=ph, orient=orient, diagonal=diagonal))
 
 
+# ------------------------------------------------------------------ recovery of the simulator's Jacobian
+JacobianRecovery = collections.namedtuple("JacobianRecovery", ("n_edges", "sign_agreement", "pearson", "spearman", "slope",
+                                                               "regulator", "target", "true", "learned"))
+
+
+def _average_ranks(v):
+    """ranks 1 .. n of a float64 vector, ties sharing the mean of their positions (scipy's rankdata, method "average")"""
+    order = np.argsort(v, kind="stable")
+    s = v[order]
+    first = np.flatnonzero(np.concatenate(([True], s[1:] != s[:-1])))      # where a run of equal values begins
+    size = np.diff(np.concatenate((first, [len(v)])))
+    ranks = np.empty(len(v), np.float64)
+    ranks[order] = np.repeat(first + (size + 1) / 2.0, size)
+    return ranks
+
+
+def _pearson(a, b):
+    if len(a) < 2:
+        return float("nan")
+    da, db = a - a.mean(), b - b.mean()
+    saa, sbb = float(da @ da), float(db @ db)
+    if not (saa > 0 and sbb > 0):                          # a constant vector has no correlation
+        return float("nan")
+    return float(min(1.0, max(-1.0, (da @ db) / np.sqrt(saa * sbb))))
+
+
+def recovery_scores(true, learned):
+    """(sign_agreement, pearson, spearman, slope) of two equally long vectors, Python floats computed in float64 on the host:
+    sign_agreement -- the share of the entries with true != 0 at which `learned` has the sign of `true` (a learned 0
+    disagrees); pearson -- the Pearson correlation; spearman -- the Pearson correlation of the average ranks; slope -- the
+    least-squares s of learned ~ s * true through the origin, sum(true * learned) / sum(true^2).  A statistic that is not
+    defined is NaN: the correlations of fewer than 2 entries or with a constant vector, the sign agreement and the slope of
+    a `true` that is 0 throughout (or empty)."""
+    t, l = np.asarray(true, np.float64).reshape(-1), np.asarray(learned, np.float64).reshape(-1)
+    if t.shape != l.shape:
+        raise ValueError("recovery_scores: true and learned must have the same length, got %d and %d" % (len(t), len(l)))
+    nz = t != 0
+    sign = float(np.mean(np.sign(t[nz]) == np.sign(l[nz]))) if nz.any() else float("nan")
+    tt = float(t @ t)
+    slope = float((t @ l) / tt) if tt > 0 else float("nan")
+    return sign, _pearson(t, l), _pearson(_average_ranks(t), _average_ranks(l)), slope
+
+
+def jacobian_recovery(odenet, system, x, diagonal=False):
+    """How well a model trained on in-silico data recovers the simulator's signed, quantitative regulatory effects: on every
+    entry of `system.jacobian_pattern()` (a `HillSystem`; the entries off the diagonal, `diagonal=True` adds the decay terms)
+    true = `system.jacobian(x, "mean")`, the simulator's d rate_target / d x_regulator averaged over the states x ([B, N] or
+    [B, 1, N], float32, on the device), is held against learned = `effects_at(odenet, regulator, target, y=x, reduce="mean")`,
+    the model's, with the bits of `jacobian_matrix(odenet, x, "mean")`.  Returns JacobianRecovery(n_edges, sign_agreement,
+    pearson, spearman, slope, regulator, target, true, learned): the four statistics of `recovery_scores(true, learned)`,
+    the entries as int64 [n_edges] and the two vectors as float32 [n_edges] on the device.  Where `network_score` asks
+    whether the edges are found, this asks whether their signs and strengths are right.
+    ValueError when the model's gene count is not `system.N`, or for an `x` of another shape."""
+    tensors = params_of(odenet)
+    if tensors[0].shape[1] != system.N:
+        raise ValueError("jacobian_recovery: the model has %d genes, the system %d" % (tensors[0].shape[1], system.N))
+    pat = system.jacobian_pattern()
+    keep = np.flatnonzero(np.ones(len(pat.regulator), bool) if diagonal else pat.regulator != pat.target)
+    learned = effects_at(odenet, pat.regulator[keep], pat.target[keep], y=x, reduce="mean")
+    jac = system.jacobian(x, "mean")
+    at = torch.from_numpy(keep).to(jac.value.device)
+    true = jac.value[at]
+    scores = recovery_scores(true.cpu().numpy(), learned.cpu().numpy())
+    return JacobianRecovery(len(keep), *scores, jac.regulator[at], jac.target[at], true, learned)
+
+
 # ------------------------------------------------------------------ pathway permutation tests (SURVEY.md row 22)
 def consolidate_gene_scores(gene_names, scores):
     """One score per gene symbol from one score per array entry (create_permutation_test_files_aws.R:68-84).  An entry

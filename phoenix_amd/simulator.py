@@ -11,8 +11,12 @@ written in the reference's CSV wire format (`csvreader.py:58-73`) so that `DataH
 Parity: the RHS is checked against Python's own evaluation of the shipped expression strings (fp64) and the
 trajectories against a tight-tolerance scipy solve of the same strings (golden G11); the R run itself cannot be
 reproduced here (its RNG draws are not recorded), which DESIGN.md states.
+The same programs are differentiated: `HillSystem.jacobian` (`phx_hill_jacobian`, `csrc/phx_hilljac.hip`) is the true
+Jacobian of the rates on its sparse pattern, the ground truth `analysis.jacobian_recovery` scores a trained model against;
+`jacobian_reference` restates it in numpy.
 """
 import ast
+import collections
 import csv
 import ctypes as C
 
@@ -278,6 +282,12 @@ def read_ode_system(path):
     return [r["node"] for r in rows], [r["eqn"] for r in rows]
 
 
+HillPattern = collections.namedtuple("HillPattern", ("regulator", "target", "ptr"))
+HillJacobian = collections.namedtuple("HillJacobian", ("regulator", "target", "value"))
+JACOBIAN_MODES = {None: 0, "mean": 1, "mean_abs": 2}     # `mode` of phx_hill_jacobian
+OP_HILL_JACOBIAN = 11    # workspace-cache key of HillSystem.jacobian (phx_hill_jacobian_workspace_bytes sizes it)
+
+
 class HillSystem:
     """The compiled rate expressions of one regulatory network, resident on the device."""
 
@@ -304,6 +314,7 @@ class HillSystem:
         self.code_host = np.asarray(code, np.int32).reshape(-1, 2)
         self.consts_host = np.asarray(consts, np.float64)
         self.off_host, self.len_host = np.asarray(off, np.int32), np.asarray(length, np.int32)
+        self._pattern = self._pattern_dev = None
         self.device = torch.device(device)
         if self.device.type == "cuda":
             self.code = torch.from_numpy(self.code_host).to(self.device)
@@ -340,6 +351,65 @@ class HillSystem:
                                                          engine._stream_ptr()))
         return out
 
+    # ---- the true Jacobian
+    def jacobian_pattern(self):
+        """The sparsity pattern of the Jacobian of the rates, on the host: HillPattern(regulator int64 [E], target int64
+        [E], ptr int64 [N + 1]) in CSR form by target -- regulator[ptr[j]:ptr[j + 1]] are the distinct genes the program of
+        gene j pushes, ascending: its regulators and, through the decay term, itself.  "input gene" rows have no entries."""
+        if self._pattern is None:
+            pushx = self.code_host[:, 0] == OPS["PUSHX"]
+            rows = [np.unique(self.code_host[o:o + n, 1][pushx[o:o + n]]) for o, n in zip(self.off_host, self.len_host)]
+            ptr = np.zeros(self.N + 1, np.int64)
+            np.cumsum([len(r) for r in rows], out=ptr[1:])
+            regulator = np.concatenate(rows).astype(np.int64) if rows else np.zeros(0, np.int64)
+            target = np.repeat(np.arange(self.N, dtype=np.int64), np.diff(ptr))
+            self._pattern = HillPattern(regulator, target, ptr)
+        return self._pattern
+
+    def _pattern_on_device(self):
+        """(eptr int64 [N + 1], ereg int32 [E], regulator int64 [E], target int64 [E]) of the pattern on the system's device"""
+        if self._pattern_dev is None:
+            pat = self.jacobian_pattern()
+            dev = self.code.device
+            self._pattern_dev = (torch.from_numpy(pat.ptr).to(dev), torch.from_numpy(pat.regulator.astype(np.int32)).to(dev),
+                                 torch.from_numpy(pat.regulator).to(dev), torch.from_numpy(pat.target).to(dev))
+        return self._pattern_dev
+
+    def jacobian(self, x, reduce=None):
+        """The true Jacobian of the rates on `jacobian_pattern()`: HillJacobian(regulator int64 [E], target int64 [E], value
+        float32) on the device, value[b, e] = d rate_target[e] / d x_regulator[e] at the state x[b] -- [B, E] with
+        reduce=None, [E] with reduce="mean" (the mean over the states) or "mean_abs" (of the absolute value; both summed in
+        float64 in an order that depends on B alone and rounded once).  x: [B, N] or [B, 1, N], float32, on the device.
+        One kernel pass (phx_hill_jacobian, include/phoenix_hip.h): a forward-mode interpretation of the compiled programs,
+        with fAct continued by 0 to TF <= 0 as `rhs` continues it."""
+        if reduce not in JACOBIAN_MODES:
+            raise ValueError('reduce must be None, "mean" or "mean_abs", got %r' % (reduce,))
+        if not isinstance(x, torch.Tensor):
+            raise TypeError("x must be a tensor on the GPU, got %s" % type(x).__name__)
+        engine._require_gpu(x, "x")
+        N = self.N
+        if not ((x.dim() == 2 and x.shape[1] == N) or (x.dim() == 3 and x.shape[1:] == (1, N))) or x.shape[0] < 1:
+            raise ValueError("x must be [B, %d] or [B, 1, %d], got %s" % (N, N, tuple(x.shape)))
+        if self.device.type != "cuda" or x.device != self.code.device:
+            raise ValueError("x is on %s, the system on %s" % (x.device, self.device))
+        eptr, ereg, regulator, target = self._pattern_on_device()
+        B, E, mode = x.shape[0], ereg.shape[0], JACOBIAN_MODES[reduce]
+        value = torch.empty((B, E) if mode == 0 else (E,), dtype=torch.float32, device=x.device)
+        if E == 0:                                       # input genes only: nothing to launch
+            return HillJacobian(regulator, target, value)
+        x2 = x.detach().reshape(B, N).contiguous()
+        lib = _lib.load()
+        nbytes = lib.phx_hill_jacobian_workspace_bytes(B, N, E, mode)
+        ws = None
+        if nbytes:
+            wkey = (x.device.index, engine._stream_raw(x.device.index), OP_HILL_JACOBIAN)
+            ws = engine._ws_cache.get(wkey)
+            if ws is None or ws.numel() < nbytes:
+                ws = engine._ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=x.device)
+        engine._check_call(lib.phx_hill_jacobian(*self._args(), engine._p(eptr), engine._p(ereg), engine._p(x2), B, N, E, mode,
+                                                 engine._p(value), engine._p(ws), nbytes, engine._stream_ptr()))
+        return HillJacobian(regulator, target, value)
+
     def sample_initial(self, numsamples, output_gene_var=1.0, rng=None, input_models=None, cor_strength=5.0,
                        input_gene_var=1.0, prop_bimodal=0.0):
         """Initial states of `simDataset` (SimulationGRN_core_init_var.R:165-213).  Regulated genes: Beta(2/var, 2/var)
@@ -358,6 +428,66 @@ class HillSystem:
                                                                 cor_strength, input_gene_var, rng)
             x[:, self.is_input] = xin
         return x.astype(np.float32)
+
+
+def jacobian_reference(system, x, dtype=np.float64, pattern=None):
+    """`HillSystem.jacobian(x)` in numpy on the host, for a system on any device (device="cpu" included): [B, E] in `dtype`,
+    entry (b, e) = d rate_target[e] / d x_regulator[e] at x[b] ([B, N] or [B, 1, N]) over `system.jacobian_pattern()` -- or
+    over another `pattern` (a HillPattern; an entry whose regulator the target's program never pushes is +0).  The same
+    forward-mode interpretation of the compiled programs as the kernel's, rule by rule (include/phoenix_hip.h), a target's
+    regulators side by side.  dtype=np.float32 rounds states and constants first and runs every operation in float32, as
+    `interpret_programs` of the oracle does for the rates: the rounding error a correct fp32 interpreter may show."""
+    x = np.asarray(x, dtype)
+    N = system.N
+    if not ((x.ndim == 2 and x.shape[1] == N) or (x.ndim == 3 and x.shape[1:] == (1, N))) or x.shape[0] < 1:
+        raise ValueError("x must be [B, %d] or [B, 1, %d], got %s" % (N, N, x.shape))
+    x = x.reshape(x.shape[0], N)
+    pat = system.jacobian_pattern() if pattern is None else pattern
+    consts = np.asarray(system.consts_host, dtype)
+    code, B = system.code_host.tolist(), x.shape[0]
+    out = np.zeros((B, len(pat.regulator)), dtype)
+    for j in range(N):
+        e0, e1 = int(pat.ptr[j]), int(pat.ptr[j + 1])
+        n = int(system.len_host[j])
+        if e0 == e1 or n == 0:
+            continue
+        regs = np.asarray(pat.regulator[e0:e1])
+        pushed = np.zeros(e1 - e0, bool)
+        zero = np.zeros((B, e1 - e0), dtype)
+        val, der = [], []                                  # [B] and [B, k]: one derivative column per regulator
+        for op, arg in code[system.off_host[j]: system.off_host[j] + n]:
+            if op == 0:
+                val.append(np.full(B, consts[arg]))
+                der.append(zero)
+            elif op == 1:
+                val.append(x[:, arg])
+                der.append(np.broadcast_to((regs == arg).astype(dtype), zero.shape))
+                pushed |= regs == arg
+            elif op == 6:
+                val[-1], der[-1] = -val[-1], -der[-1]
+            elif op == 7:
+                b, k, nn = consts[arg: arg + 3]
+                tf, on = val[-1], val[-1] > 0
+                tfp = np.where(on, np.abs(tf), dtype(1))
+                tn = np.where(on, tfp ** nn, dtype(0))
+                den = k + tn
+                val[-1] = b * tn / den
+                slope = np.where(on, b * k * nn * tfp ** (nn - dtype(1)) / (den * den), dtype(0))
+                der[-1] = np.where(on[:, None], slope[:, None] * der[-1], dtype(0))
+            else:
+                r, rd = val.pop(), der.pop()
+                l, ld = val[-1], der[-1]
+                if op == 2:
+                    val[-1], der[-1] = l + r, ld + rd
+                elif op == 3:
+                    val[-1], der[-1] = l - r, ld - rd
+                elif op == 4:
+                    val[-1], der[-1] = l * r, ld * r[:, None] + l[:, None] * rd
+                else:
+                    q = l / r
+                    val[-1], der[-1] = q, (ld - q[:, None] * rd) / r[:, None]
+        out[:, e0:e1] = np.where(pushed[None, :], der[0], dtype(0))
+    return out
 
 
 def generate_dataset(system, numsamples, time_stamps=(0.0, 2.0, 3.0, 7.0, 9.0), expnoise=0.0, dt_max=0.01, rng=None,
