@@ -127,16 +127,9 @@ def jacobian_matrix(odenet, y, reduce="mean_abs", rows=None, out=None):
     (reduce="mean_abs"): the state-dependent regulator -> target network that the influence scan samples by perturbation
     and of which `effects_matrix` is the crude, state-free form.  float32 [R, N] on the device; `rows` and `out` as for
     `effects_matrix`.  One kernel call: the [N, N] Jacobians of the states are never formed."""
-    if reduce not in ("mean", "mean_abs"):
-        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
-    tensors = params_of(odenet)
-    N = tensors[0].shape[1]
-    rows = engine.check_rows(rows, N)
-    engine._require_gpu(tensors[0], "odenet")
     with torch.no_grad():
-        p = engine.params_cached(*tensors)
-        y2, ph = _states(p, y)
-        return engine.effects_matrix(p, reduce, y=y2, ph=ph, rows=rows, out=out)
+        p, mode, y2, ph, rows = _model_states(odenet, y, reduce, lambda N: engine.check_rows(rows, N), need_y=True)
+        return engine.effects_matrix(p, mode, y=y2, ph=ph, rows=rows, out=out)
 
 
 def _states(p, y):
@@ -149,6 +142,22 @@ def _states(p, y):
     # the product branch's hidden vector of every state (odenet.py:87-88): a [B, N] x [N, H] contraction, plumbing
     s = y2 - 0.5
     return y2, torch.exp(torch.addmm(p.bp, torch.log1p(s / (1 + s.abs())), p.Wp.t()))
+
+
+def _model_states(odenet, y, reduce, host_check=None, name=None, need_y=False):
+    """What the analyses of the effects tile engine do before they call it, host errors first: the `reduce` check (its
+    message starts with `name` where one is given), then host_check(N) -- the caller's ValueErrors that need the gene
+    count -- and only then the requirement of a GPU.  Returns (Params, mode, y2, ph, what host_check returned): mode is
+    "effects" and the states are None when `y` is None (never with `need_y`), else mode is `reduce`."""
+    states = need_y or y is not None
+    if states and reduce not in ("mean", "mean_abs"):
+        raise ValueError('%sreduce must be "mean" or "mean_abs", got %r' % (name + ": " if name else "", reduce))
+    tensors = params_of(odenet)
+    checked = host_check(tensors[0].shape[1]) if host_check else None
+    engine._require_gpu(tensors[0], "odenet")
+    p = engine.params_cached(*tensors)
+    y2, ph = _states(p, y) if states else (None, None)
+    return p, reduce if states else "effects", y2, ph, checked
 
 
 Edges = collections.namedtuple("Edges", ("regulator", "target", "value"))
@@ -166,16 +175,10 @@ def effects_edges(odenet, top=None, threshold=None, orient=False, diagonal=False
     The kernel recomputes the tiles in every pass (count, at most one refinement, emit), so with `y` each pass repeats the
     loop over the states; `threshold` with `max_edges` is one pass into a list of that capacity and raises RuntimeError,
     naming the true count, when more entries qualify."""
-    if y is not None and reduce not in ("mean", "mean_abs"):
-        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
-    engine.check_edges_selection(top, threshold, max_edges)
-    tensors = params_of(odenet)
-    engine._require_gpu(tensors[0], "odenet")
     with torch.no_grad():
-        p = engine.params_cached(*tensors)
-        y2, ph = (None, None) if y is None else _states(p, y)
-        return Edges(*engine.effects_edges(p, "effects" if y is None else reduce, y=y2, ph=ph, top=top, threshold=threshold,
-                                           orient=orient, diagonal=diagonal, max_edges=max_edges))
+        p, mode, y2, ph, _ = _model_states(odenet, y, reduce, lambda N: engine.check_edges_selection(top, threshold, max_edges))
+        return Edges(*engine.effects_edges(p, mode, y=y2, ph=ph, top=top, threshold=threshold, orient=orient,
+                                           diagonal=diagonal, max_edges=max_edges))
 
 
 Neighbors = collections.namedtuple("Neighbors", ("gene", "value", "count", "strength"))
@@ -195,17 +198,11 @@ def effects_neighbors(odenet, k, of="target", regulators=None, targets=None, thr
     is in `targets` (sequences or tensors of gene indices, duplicates count once, None: all genes; e.g. a transcription-factor
     list, as get_link_list of GRN_rnaode.py:43-181 takes one) and, with `threshold` (positive, finite), |value| >= threshold.
     1 <= k <= 64.  One kernel call; the results are bitwise reproducible."""
-    if y is not None and reduce not in ("mean", "mean_abs"):
-        raise ValueError('reduce must be "mean" or "mean_abs", got %r' % (reduce,))
-    tensors = params_of(odenet)
-    k, _, regulators, targets = engine.check_neighbors_selection(k, of, regulators, targets, threshold, tensors[0].shape[1])
-    engine._require_gpu(tensors[0], "odenet")
     with torch.no_grad():
-        p = engine.params_cached(*tensors)
-        y2, ph = (None, None) if y is None else _states(p, y)
-        return Neighbors(*engine.effects_neighbors(p, "effects" if y is None else reduce, k, of=of, y=y2, ph=ph,
-                                                   regulators=regulators, targets=targets, threshold=threshold,
-                                                   orient=orient, diagonal=diagonal))
+        p, mode, y2, ph, (k, _, regulators, targets) = _model_states(
+            odenet, y, reduce, lambda N: engine.check_neighbors_selection(k, of, regulators, targets, threshold, N))
+        return Neighbors(*engine.effects_neighbors(p, mode, k, of=of, y=y2, ph=ph, regulators=regulators, targets=targets,
+                                                   threshold=threshold, orient=orient, diagonal=diagonal))
 
 
 def write_link_list(fp, edges, gene_names=None, signed=False, of=None):
@@ -285,14 +282,9 @@ NetworkScore = collections.namedtuple("NetworkScore", ("auroc", "average_precisi
 def _network_call(name, odenet, regulator, target, y, reduce):
     """the checks `effects_at` and `network_score` share, in the order host errors first: (Params, mode, y2, ph, regulator,
     target) with the index tensors on the model's device"""
-    if y is not None and reduce not in ("mean", "mean_abs"):
-        raise ValueError('%s: reduce must be "mean" or "mean_abs", got %r' % (name, reduce))
-    tensors = params_of(odenet)
-    regulator, target = engine.check_network_indices(name, regulator, target, tensors[0].shape[1])
-    engine._require_gpu(tensors[0], "odenet")
-    p = engine.params_cached(*tensors)
-    y2, ph = (None, None) if y is None else _states(p, y)
-    return p, "effects" if y is None else reduce, y2, ph, regulator.to(p.device), target.to(p.device)
+    p, mode, y2, ph, (regulator, target) = _model_states(
+        odenet, y, reduce, lambda N: engine.check_network_indices(name, regulator, target, N), name=name)
+    return p, mode, y2, ph, regulator.to(p.device), target.to(p.device)
 
 
 def effects_at(odenet, regulator, target, orient=False, y=None, reduce="mean_abs"):

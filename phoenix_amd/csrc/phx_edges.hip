@@ -10,6 +10,7 @@
 //                 same image, writes that one to LDS (64 rows of 68 floats, 17 KiB over the dead image: a lane's four
 //                 partner rows lie 16 banks apart) and reads it back transposed, so that the lane that holds M[i,j] also
 //                 holds M[j,i] and decides both directions of the gene pair, once.  A diagonal tile is its own partner.
+//                 That sequence is efx_tile_pair of phx_effects_tile.inc, which k_rank (phx_netscore.hip) shares.
 //                 Both tiles come from efx_tile<MODE>, the code that k_effects stores: every value has the bits that
 //                 phx_effects_matrix writes for that entry (chain k ascending, b ascending, mean, then relu(g_j)).
 //   COUNT pass    A 4096-bin histogram of m: level 0 on its top 12 bits (m >> 19), level 1 on the next 12 ((m >> 7) & 4095)
@@ -25,6 +26,7 @@
 
 #include <cstddef>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/phoenix_hip.h"
 #include "phx_host.hpp"
@@ -34,9 +36,6 @@ namespace {
 #include "phx_effects_tile.inc"
 
 constexpr int EDG_BINS = 4096;
-constexpr int EDG_TLD = 68;                          // floats of a row of the transposed tile
-constexpr int EDG_TBUF = EFX_TILE * EDG_TLD;         // 4352 floats
-constexpr unsigned EDG_INF = 0x7f800000u;            // m < EDG_INF: finite;  m <= EDG_INF: not a NaN
 constexpr size_t EDG_WS_BYTES = (EDG_BINS + 16) * sizeof(unsigned);   // the histogram, the cursor, padding
 
 struct edges_args {
@@ -62,54 +61,23 @@ __global__ __launch_bounds__(EFX_THREADS) void k_edges(const float *__restrict__
     const int iw = (wv & 1) * 32, jw = (wv >> 1) * 32;
     const int T = (N + EFX_TILE - 1) / EFX_TILE;
     int I, J;
-    if (ORIENT) {
-        // blockIdx.x = J (J + 1) / 2 + I with I <= J: the root by float, then made exact
-        const int p = blockIdx.x;
-        J = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
-        while ((J + 1) * (J + 2) / 2 <= p) ++J;
-        while (J * (J + 1) / 2 > p) --J;
-        I = p - J * (J + 1) / 2;
-    } else {
-        I = blockIdx.x / T;
-        J = blockIdx.x - I * T;
-    }
+    efx_tile_of_block(ORIENT, T, I, J);
     const int i0 = I * EFX_TILE, j0 = J * EFX_TILE;
 
     f4 va[2][2];                   // tile (I, J)
     f4 vp[2][2];                   // ORIENT: vp[ti][tj][r] = M[j, i] for the entry (i, j) of va[ti][tj][r]
-    efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, i0, j0, va);
-    float *tbuf = lds;
-    unsigned *hist = reinterpret_cast<unsigned *>(lds + (ORIENT ? EDG_TBUF : 0));
+    unsigned *hist = reinterpret_cast<unsigned *>(lds + (ORIENT ? EFX_TBUF : 0));     // behind the transposed tile
+    const auto zero_hist = [=] {
+        if (a.pass == PHX_EDGES_COUNT)
+            for (int b = tid; b < EDG_BINS; b += EFX_THREADS) hist[b] = 0;
+    };
     if (ORIENT) {
-        f4 vb[2][2];               // tile (J, I)
-        if (I != J) {
-            __syncthreads();       // every wave is done with the image of tile (I, J)
-            efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, j0, i0, vb);
-        } else {
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj) vb[ti][tj] = va[ti][tj];
-        }
-        __syncthreads();           // the image is dead: the transposed tile takes its place
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-                *reinterpret_cast<f4 *>(tbuf + (iw + 16 * ti + lc) * EDG_TLD + jw + 16 * tj + 4 * lq) = vb[ti][tj];
+        efx_tile_pair<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, I, J, iw + lc, jw + 4 * lq, va, vp, zero_hist);
     } else {
+        efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, i0, j0, va);
+        __syncthreads();           // the image is dead: the histogram takes its place
+        zero_hist();
         __syncthreads();
-    }
-    if (a.pass == PHX_EDGES_COUNT)
-        for (int b = tid; b < EDG_BINS; b += EFX_THREADS) hist[b] = 0;
-    __syncthreads();
-    if (ORIENT) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) vp[ti][tj][r] = tbuf[(jw + 16 * tj + 4 * lq + r) * EDG_TLD + iw + 16 * ti + lc];
     }
 
     // which of this lane's entries take part in this pass: bit 4 (2 ti + tj) + r of `fwd` for (i, j), of `rev` for (j, i)
@@ -130,10 +98,10 @@ __global__ __launch_bounds__(EFX_THREADS) void k_edges(const float *__restrict__
                 unsigned mb = 0;
                 if (ORIENT) {
                     mb = __float_as_uint(vp[ti][tj][r]) & 0x7fffffffu;
-                    ef = inside && i != j && ma != 0 && ma < EDG_INF && mb <= EDG_INF && ma > mb;
-                    er = inside && I != J && mb != 0 && mb < EDG_INF && ma <= EDG_INF && mb > ma;
+                    ef = inside && i != j && ma != 0 && ma < EFX_INF && mb <= EFX_INF && ma > mb;
+                    er = inside && I != J && mb != 0 && mb < EFX_INF && ma <= EFX_INF && mb > ma;
                 } else {
-                    ef = inside && ma != 0 && ma < EDG_INF && (i != j || a.diagonal);
+                    ef = inside && ma != 0 && ma < EFX_INF && (i != j || a.diagonal);
                 }
                 if (count) {
                     if (a.level) {
@@ -214,13 +182,10 @@ __global__ __launch_bounds__(EFX_THREADS) void k_edges(const float *__restrict__
     }
 }
 
-// i N + j must fit 32 bits of the key
-bool edges_shape_ok(int N, int H) { return effects_shape_ok(N, H) && N <= 65535; }
-
 size_t edges_lds_bytes(int H, int mode, bool orient, int pass)
 {
     const size_t tile = effects_lds_bytes(H, mode);
-    const size_t tail = ((orient ? EDG_TBUF : 0) + (pass == PHX_EDGES_COUNT ? EDG_BINS : 0)) * sizeof(float);
+    const size_t tail = ((orient ? EFX_TBUF : 0) + (pass == PHX_EDGES_COUNT ? EDG_BINS : 0)) * sizeof(float);
     return tile > tail ? tile : tail;
 }
 
@@ -229,17 +194,9 @@ int edges_launch(const phx_params *p, const float *y, const float *ph, int B, co
 {
     const size_t lds = edges_lds_bytes(p->H, MODE, ORIENT, a.pass);
     if (!phxh::set_lds(k_edges<MODE, ORIENT>, lds)) return PHX_ERR_LAUNCH;
-    const int T = (p->N + EFX_TILE - 1) / EFX_TILE;
-    const dim3 grid(ORIENT ? T * (T + 1) / 2 : T * T);
-    hipLaunchKernelGGL((k_edges<MODE, ORIENT>), grid, dim3(EFX_THREADS), lds, st, p->Ws, p->Wp, p->WaT, p->g, y, ph, p->N, p->H,
-                       B, a);
+    hipLaunchKernelGGL((k_edges<MODE, ORIENT>), dim3(efx_pair_grid(p->N, ORIENT)), dim3(EFX_THREADS), lds, st, p->Ws, p->Wp,
+                       p->WaT, p->g, y, ph, p->N, p->H, B, a);
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
-}
-
-template <int MODE>
-int edges_launch(const phx_params *p, const float *y, const float *ph, int B, bool orient, const edges_args &a, hipStream_t st)
-{
-    return orient ? edges_launch<MODE, true>(p, y, ph, B, a, st) : edges_launch<MODE, false>(p, y, ph, B, a, st);
 }
 
 }  // namespace
@@ -248,8 +205,7 @@ extern "C" {
 
 size_t phx_effects_edges_workspace_bytes(int N, int H, int B, int mode)
 {
-    if (!edges_shape_ok(N, H)) return 0;
-    if (mode != PHX_EFFECTS && mode != PHX_JAC_MEAN && mode != PHX_JAC_MEAN_ABS) return 0;
+    if (!efx_pair_shape_ok(N, H) || !efx_mode_ok(mode)) return 0;     // i N + j must fit 32 bits of the key
     if (mode != PHX_EFFECTS && B < 1) return 0;
     return EDG_WS_BYTES;
 }
@@ -258,19 +214,17 @@ int phx_effects_edges(const phx_params *p, int mode, const float *y, const float
                       unsigned prefix, float tau, long long *keys, float *values, unsigned capacity, void *workspace,
                       size_t workspace_bytes, void *stream)
 {
-    if (!p || !p->Ws || !p->Wp || !p->WaT || !p->g || !edges_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
-    if (mode != PHX_EFFECTS && mode != PHX_JAC_MEAN && mode != PHX_JAC_MEAN_ABS) return PHX_ERR_BAD_ARG;
-    if (mode != PHX_EFFECTS && (!y || !ph || B < 1)) return PHX_ERR_BAD_ARG;
-    if (flags & ~(PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_args_ok(p, mode, y, ph, B, flags, PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_pair_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
     unsigned lo = 0;
     if (pass == PHX_EDGES_COUNT) {
         // level-0 bins from 0xff0 up hold infinities and NaNs, which are never eligible
         if (level != 0 && level != 1) return PHX_ERR_BAD_ARG;
-        if (level == 1 && prefix >= (EDG_INF >> 19)) return PHX_ERR_BAD_ARG;
+        if (level == 1 && prefix >= (EFX_INF >> 19)) return PHX_ERR_BAD_ARG;
     } else if (pass == PHX_EDGES_EMIT) {
         if (!keys || !values || capacity < 1) return PHX_ERR_BAD_ARG;
         std::memcpy(&lo, &tau, sizeof lo);
-        if (!(tau > 0.f) || lo >= EDG_INF) return PHX_ERR_BAD_ARG;      // tau positive and finite (subnormals count)
+        if (!(tau > 0.f) || lo >= EFX_INF) return PHX_ERR_BAD_ARG;      // tau positive and finite (subnormals count)
     } else {
         return PHX_ERR_BAD_ARG;
     }
@@ -291,12 +245,10 @@ int phx_effects_edges(const phx_params *p, int mode, const float *y, const float
     const hipError_t e = pass == PHX_EDGES_COUNT ? hipMemsetAsync(a.hist, 0, EDG_BINS * sizeof(unsigned), st)
                                                  : hipMemsetAsync(a.cursor, 0, sizeof(unsigned), st);
     if (e != hipSuccess) return PHX_ERR_LAUNCH;
-    const bool orient = (flags & PHX_EDGES_ORIENT) != 0;
-    switch (mode) {
-    case PHX_EFFECTS: return edges_launch<PHX_EFFECTS>(p, nullptr, nullptr, 1, orient, a, st);
-    case PHX_JAC_MEAN: return edges_launch<PHX_JAC_MEAN>(p, y, ph, B, orient, a, st);
-    default: return edges_launch<PHX_JAC_MEAN_ABS>(p, y, ph, B, orient, a, st);
-    }
+    return efx_dispatch(mode, (flags & PHX_EDGES_ORIENT) != 0, y, ph, B,
+                        [&](auto MODE, auto ORIENT, const float *ys, const float *phs, int Bs) {
+                            return edges_launch<decltype(MODE)::value, decltype(ORIENT)::value>(p, ys, phs, Bs, a, st);
+                        });
 }
 
 }  // extern "C"

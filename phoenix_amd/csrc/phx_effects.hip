@@ -30,11 +30,13 @@
 // Every entry is one lane's chain of fused multiply-adds over k = 0 .. Hp - 1 in that order (padding rows are zeros) and,
 // in the Jacobian modes, over b = 0 .. B - 1 in that order: its bits depend on (N, H, B, mode, i, j) alone, not on the row
 // range or the tile it falls into.  No atomics.
-// The image, the K loops and the tile itself (efx_tile<MODE>) live in phx_effects_tile.inc, which phx_edges.hip shares: this
-// unit stores the finished tile, that one selects edges from it.
+// The image, the K loops and the tile itself (efx_tile<MODE>) live in phx_effects_tile.inc, which phx_edges.hip,
+// phx_netscore.hip and phx_neighbors.hip share: this unit stores the finished tile, those select from it.  The argument
+// checks and the mode dispatch of the entry point are the shared ones of that file as well.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <type_traits>
 
 #include "../../include/phoenix_hip.h"
 #include "phx_host.hpp"
@@ -103,19 +105,15 @@ size_t phx_effects_workspace_bytes(int N, int H, int B, int mode)
 int phx_effects_matrix(const phx_params *p, int mode, const float *y, const float *ph, int B, int row0, int row1, float *out,
                        void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!p || !out || !p->Ws || !p->Wp || !p->WaT || !p->g || !effects_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
+    if (!efx_args_ok(p, mode, y, ph, B, 0, 0) || !out) return PHX_ERR_BAD_ARG;
     if (row0 < 0 || row1 > p->N || row0 >= row1) return PHX_ERR_BAD_ARG;
-    if (mode != PHX_EFFECTS && mode != PHX_JAC_MEAN && mode != PHX_JAC_MEAN_ABS) return PHX_ERR_BAD_ARG;
-    if (mode != PHX_EFFECTS && (!y || !ph || B < 1)) return PHX_ERR_BAD_ARG;
     if ((row1 - row0 + EFX_TILE - 1) / EFX_TILE > 65535) return PHX_ERR_BAD_ARG;
     const size_t need = phx_effects_workspace_bytes(p->N, p->H, B, mode);
     if (workspace_bytes < need || (need && !workspace)) return PHX_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    switch (mode) {
-    case PHX_EFFECTS: return effects_launch<PHX_EFFECTS>(p, nullptr, nullptr, 1, row0, row1, out, st);
-    case PHX_JAC_MEAN: return effects_launch<PHX_JAC_MEAN>(p, y, ph, B, row0, row1, out, st);
-    default: return effects_launch<PHX_JAC_MEAN_ABS>(p, y, ph, B, row0, row1, out, st);
-    }
+    return efx_dispatch(mode, false, y, ph, B, [&](auto MODE, auto, const float *ys, const float *phs, int Bs) {
+        return effects_launch<decltype(MODE)::value>(p, ys, phs, Bs, row0, row1, out, st);
+    });
 }
 
 }  // extern "C"

@@ -1,7 +1,10 @@
-// phx_effects_tile.inc -- the 64 x 64 tile engine shared by phx_effects.hip (which stores the tile) and phx_edges.hip
-// (which selects edges from it): the LDS image, the K loops and efx_tile<MODE>, which leaves one finished tile of the
-// regulator -> target matrix in the MFMA accumulator layout.  Included inside an anonymous namespace after
-// <hip/hip_runtime.h> and include/phoenix_hip.h; the layout and the chain order are described in phx_effects.hip.
+// phx_effects_tile.inc -- the 64 x 64 tile engine shared by phx_effects.hip (which stores the tile) and its epilogue units
+// phx_edges.hip, phx_netscore.hip and phx_neighbors.hip (which select from it): the LDS image, the K loops and
+// efx_tile<MODE>, which leaves one finished tile of the regulator -> target matrix in the MFMA accumulator layout, and
+// behind them what the units share around the tile: the block-to-tile decoding, the parked tile, the tile pair of the
+// oriented kernels, the argument checks and the <MODE, ORIENT> launch dispatch.  Included inside an anonymous namespace
+// after <hip/hip_runtime.h>, <type_traits> and include/phoenix_hip.h; the layout and the chain order are described in
+// phx_effects.hip.
 
 constexpr int EFX_TILE = 64;       // regulators and targets of a workgroup
 constexpr int EFX_LD = 144;        // floats of an LDS row: 64 regulator columns | 64 target columns | 16 padding
@@ -202,4 +205,120 @@ inline size_t effects_lds_bytes(int H, int mode)
     const int Hp = (H + 3) & ~3;
     if (mode == PHX_EFFECTS) return (size_t)(Hp < EFX_KC ? Hp : EFX_KC) * EFX_LD * sizeof(float);
     return ((size_t)Hp * EFX_LD + EFX_LDS_TAIL) * sizeof(float);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// What the epilogue kernels (k_edges, k_gather, k_rank, k_neighbors) share around the tile.  Device side first.
+constexpr int EFX_TLD = 68;                          // floats of a row of a parked tile: a lane's four rows lie 16 banks apart
+constexpr int EFX_TBUF = EFX_TILE * EFX_TLD;         // 4352 floats
+constexpr unsigned EFX_INF = 0x7f800000u;            // magnitude bits m < EFX_INF: finite;  m <= EFX_INF: not a NaN
+
+// The tile (I, J) of workgroup blockIdx.x on the T x T tile grid; with `orient` the unordered pair I <= J of the
+// T (T + 1) / 2 workgroups of efx_pair_grid
+__device__ __forceinline__ void efx_tile_of_block(bool orient, int T, int &I, int &J)
+{
+    if (orient) {
+        // blockIdx.x = J (J + 1) / 2 + I with I <= J: the root by float, then made exact
+        const int p = blockIdx.x;
+        J = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
+        while ((J + 1) * (J + 2) / 2 <= p) ++J;
+        while (J * (J + 1) / 2 > p) --J;
+        I = p - J * (J + 1) / 2;
+    } else {
+        I = blockIdx.x / T;
+        J = blockIdx.x - I * T;
+    }
+}
+
+// parks a tile of the accumulator layout in LDS, ta[il * EFX_TLD + jl] = entry (i0 + il, j0 + jl), as four 16-byte stores,
+// and with `both` a second tile vb in tb the same way, quad by quad beside the first.  (row, col) = (iw + lc, jw + 4 lq),
+// this lane's first entry in the tile: the caller has them from its kernel's entry
+__device__ __forceinline__ void efx_park(float *ta, const f4 (&va)[2][2], float *tb, const f4 (&vb)[2][2], bool both, int row,
+                                         int col)
+{
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj) {
+            *reinterpret_cast<f4 *>(ta + (row + 16 * ti) * EFX_TLD + col + 16 * tj) = va[ti][tj];
+            if (both) *reinterpret_cast<f4 *>(tb + (row + 16 * ti) * EFX_TLD + col + 16 * tj) = vb[ti][tj];
+        }
+}
+
+// Leaves va = tile (I, J) and vp[ti][tj][r] = M[j, i] for the entry (i, j) of va[ti][tj][r]: forms tile (J, I) in the same
+// image (a diagonal tile is its own partner), parks it over the dead image (EFX_TBUF floats at `lds`) and reads it back
+// transposed, so that one lane holds both directions of a gene pair.  (row, col) as for efx_park.  between() runs after
+// the store of the partner tile and before the barrier in front of the transposed read: the place for a caller's own LDS
+// setup outside those EFX_TBUF floats.  Every thread of the workgroup calls it; tile (I, J) alone costs no barrier, the
+// partner three (two when I == J).
+template <int MODE, class Between>
+__device__ __forceinline__ void efx_tile_pair(float *lds, const float *__restrict__ Ws, const float *__restrict__ Wp,
+                                              const float *__restrict__ WaT, const float *__restrict__ g,
+                                              const float *__restrict__ y, const float *__restrict__ ph, int N, int H, int B,
+                                              int I, int J, int row, int col, f4 (&va)[2][2], f4 (&vp)[2][2], Between between)
+{
+    const int i0 = I * EFX_TILE, j0 = J * EFX_TILE;
+    efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, i0, j0, va);
+    f4 vb[2][2];                   // tile (J, I)
+    if (I != J) {
+        __syncthreads();           // every wave is done with the image of tile (I, J)
+        efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, j0, i0, vb);
+    } else {
+#pragma unroll
+        for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+            for (int tj = 0; tj < 2; ++tj) vb[ti][tj] = va[ti][tj];
+    }
+    __syncthreads();               // the image is dead: the transposed tile takes its place
+    efx_park(lds, vb, lds, vb, false, row, col);
+    between();
+    __syncthreads();
+#pragma unroll
+    for (int ti = 0; ti < 2; ++ti)
+#pragma unroll
+        for (int tj = 0; tj < 2; ++tj)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vp[ti][tj][r] = lds[(col + 16 * tj + r) * EFX_TLD + row + 16 * ti];
+}
+
+// Host side: the argument checks and the launch dispatch of the four entry points.
+inline bool efx_mode_ok(int mode) { return mode == PHX_EFFECTS || mode == PHX_JAC_MEAN || mode == PHX_JAC_MEAN_ABS; }
+
+// the shapes of the kernels whose keys hold i N + j in 32 bits (or a gene index in 16)
+inline bool efx_pair_shape_ok(int N, int H) { return effects_shape_ok(N, H) && N <= 65535; }
+
+// p and its four pointers, the shape (effects_shape_ok: a caller with keys adds efx_pair_shape_ok), the mode, the states of
+// the Jacobian modes and the flag bits
+inline bool efx_args_ok(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, int allowed_flags)
+{
+    if (!p || !p->Ws || !p->Wp || !p->WaT || !p->g || !effects_shape_ok(p->N, p->H)) return false;
+    if (!efx_mode_ok(mode)) return false;
+    if (mode != PHX_EFFECTS && (!y || !ph || B < 1)) return false;
+    return !(flags & ~allowed_flags);
+}
+
+// workgroups of a kernel that decodes its tile with efx_tile_of_block
+inline int efx_pair_grid(int N, bool orient)
+{
+    const int T = (N + EFX_TILE - 1) / EFX_TILE;
+    return orient ? T * (T + 1) / 2 : T * T;
+}
+
+// launch(MODE, ORIENT, y, ph, B) with the (checked) mode and the orientation as std::integral_constant arguments, so that a
+// generic lambda picks its kernel instantiation from their types; PHX_EFFECTS has no states: (nullptr, nullptr, 1)
+template <class Launch>
+int efx_dispatch(int mode, bool orient, const float *y, const float *ph, int B, Launch &&launch)
+{
+    if (mode == PHX_EFFECTS) {
+        y = ph = nullptr;
+        B = 1;
+    }
+    const auto oriented = [&](auto MODE) {
+        return orient ? launch(MODE, std::true_type(), y, ph, B) : launch(MODE, std::false_type(), y, ph, B);
+    };
+    switch (mode) {
+    case PHX_EFFECTS: return oriented(std::integral_constant<int, PHX_EFFECTS>());
+    case PHX_JAC_MEAN: return oriented(std::integral_constant<int, PHX_JAC_MEAN>());
+    default: return oriented(std::integral_constant<int, PHX_JAC_MEAN_ABS>());
+    }
 }

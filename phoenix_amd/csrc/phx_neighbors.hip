@@ -30,6 +30,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/phoenix_hip.h"
 #include "phx_host.hpp"
@@ -43,7 +44,6 @@ typedef unsigned long long u64;
 constexpr int NBR_LD = 65;                           // floats of a row of a parked tile
 constexpr int NBR_TBUF = EFX_TILE * NBR_LD;          // 4160 floats
 constexpr int NBR_HEAD = 16;                         // floats in front of the image: the 64 candidate bytes of the streamed tile
-constexpr unsigned NBR_INF = 0x7f800000u;            // m < NBR_INF: finite;  m <= NBR_INF: not a NaN
 constexpr int NBR_MAX_K = 64;
 constexpr int NBR_MAX_SEG = 8;
 constexpr int NBR_WORKGROUPS = 1024;                 // the segment rule aims at this many workgroups
@@ -166,10 +166,10 @@ __global__ __launch_bounds__(EFX_THREADS) void k_neighbors(const float *__restri
             const int o = 16 * q + e, go = o0 + o;
             const float v = ta[e_base + o * e_step];
             const unsigned m = __float_as_uint(v) & 0x7fffffffu;
-            bool ok = line_ok && oks[o] && m != 0 && m < NBR_INF && m >= a.lo;
+            bool ok = line_ok && oks[o] && m != 0 && m < EFX_INF && m >= a.lo;
             if (ORIENT) {
                 const unsigned mb = __float_as_uint(tb[p_base + o * p_step]) & 0x7fffffffu;
-                ok = ok && go != gl && mb <= NBR_INF && m > mb;
+                ok = ok && go != gl && mb <= EFX_INF && m > mb;
             } else {
                 ok = ok && (go != gl || a.diagonal);
             }
@@ -260,11 +260,6 @@ __global__ __launch_bounds__(EFX_THREADS) void k_neighbors_merge(const u64 *__re
     }
 }
 
-// the other gene's index must fit 16 bits of the key
-bool nbr_shape_ok(int N, int H) { return effects_shape_ok(N, H) && N <= 65535; }
-
-bool nbr_mode_ok(int mode) { return mode == PHX_EFFECTS || mode == PHX_JAC_MEAN || mode == PHX_JAC_MEAN_ABS; }
-
 // segments of the streamed dimension: enough for NBR_WORKGROUPS workgroups, at most NBR_MAX_SEG and one per streamed tile.
 // A function of N alone (PHX_NEIGHBORS_SEGMENTS=<n> forces n, clamped the same way), so the strengths are too.
 int nbr_segments(int N)
@@ -310,19 +305,13 @@ int nbr_launch(const phx_params *p, const float *y, const float *ph, int B, cons
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
 }
 
-template <int MODE>
-int nbr_launch(const phx_params *p, const float *y, const float *ph, int B, bool orient, const nbr_args &a, hipStream_t st)
-{
-    return orient ? nbr_launch<MODE, true>(p, y, ph, B, a, st) : nbr_launch<MODE, false>(p, y, ph, B, a, st);
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t phx_effects_neighbors_workspace_bytes(int N, int H, int B, int mode, int axis, int k)
 {
-    if (!nbr_shape_ok(N, H) || !nbr_mode_ok(mode)) return 0;
+    if (!efx_pair_shape_ok(N, H) || !efx_mode_ok(mode)) return 0;     // the other gene's index must fit 16 bits of the key
     if (mode != PHX_EFFECTS && B < 1) return 0;
     if (axis != PHX_NEIGHBORS_OF_REGULATOR && axis != PHX_NEIGHBORS_OF_TARGET) return 0;
     if (k < 1 || k > NBR_MAX_K) return 0;
@@ -333,15 +322,13 @@ int phx_effects_neighbors(const phx_params *p, int mode, const float *y, const f
                           float tau, const unsigned char *regulator_ok, const unsigned char *target_ok, int *gene, float *value,
                           unsigned *count, float *strength, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!p || !p->Ws || !p->Wp || !p->WaT || !p->g || !nbr_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
-    if (!nbr_mode_ok(mode)) return PHX_ERR_BAD_ARG;
-    if (mode != PHX_EFFECTS && (!y || !ph || B < 1)) return PHX_ERR_BAD_ARG;
-    if (flags & ~(PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_args_ok(p, mode, y, ph, B, flags, PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_pair_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
     if (axis != PHX_NEIGHBORS_OF_REGULATOR && axis != PHX_NEIGHBORS_OF_TARGET) return PHX_ERR_BAD_ARG;
     if (k < 1 || k > NBR_MAX_K) return PHX_ERR_BAD_ARG;
     unsigned lo = 0;
     std::memcpy(&lo, &tau, sizeof lo);
-    if (!(tau >= 0.f) || lo >= NBR_INF) return PHX_ERR_BAD_ARG;         // +0 (no threshold) or positive and finite
+    if (!(tau >= 0.f) || lo >= EFX_INF) return PHX_ERR_BAD_ARG;         // +0 (no threshold) or positive and finite
     if (!gene || !value || !count || !strength) return PHX_ERR_BAD_ARG;
     const int S = nbr_segments(p->N);
     const nbr_layout w = nbr_workspace(p->N, k, S);
@@ -360,13 +347,10 @@ int phx_effects_neighbors(const phx_params *p, int mode, const float *y, const f
     a.S = S;
     a.axis = axis;
     a.diagonal = (flags & PHX_EDGES_DIAGONAL) != 0;
-    const bool orient = (flags & PHX_EDGES_ORIENT) != 0;
-    int rc;
-    switch (mode) {
-    case PHX_EFFECTS: rc = nbr_launch<PHX_EFFECTS>(p, nullptr, nullptr, 1, orient, a, st); break;
-    case PHX_JAC_MEAN: rc = nbr_launch<PHX_JAC_MEAN>(p, y, ph, B, orient, a, st); break;
-    default: rc = nbr_launch<PHX_JAC_MEAN_ABS>(p, y, ph, B, orient, a, st); break;
-    }
+    const int rc = efx_dispatch(mode, (flags & PHX_EDGES_ORIENT) != 0, y, ph, B,
+                                [&](auto MODE, auto ORIENT, const float *ys, const float *phs, int Bs) {
+                                    return nbr_launch<decltype(MODE)::value, decltype(ORIENT)::value>(p, ys, phs, Bs, a, st);
+                                });
     if (rc != PHX_OK) return rc;
     const int N = p->N, Np = (N + EFX_TILE - 1) / EFX_TILE * EFX_TILE;
     hipLaunchKernelGGL(k_neighbors_merge, dim3((N + NBR_MERGE_LINES - 1) / NBR_MERGE_LINES), dim3(EFX_THREADS), 0, st, a.keys,

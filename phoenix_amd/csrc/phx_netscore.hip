@@ -7,7 +7,8 @@
 // floats (a NaN on either side fails the comparison), every other entry and the diagonal are +0.
 //
 //   tiles         As k_edges: without ORIENT a workgroup owns tile (I, J); with ORIENT the unordered pair I <= J, forms
-//                 both tiles and decides both directions of every gene pair once.
+//                 both tiles and decides both directions of every gene pair once (efx_tile_of_block, efx_park and
+//                 efx_tile_pair of phx_effects_tile.inc).
 //   GATHER pass   keys[n] = i N + j grouped by tile (segment t = I T + J is keys[off[t] .. off[t + 1])); values[n] = the
 //                 scored matrix's entry.  A workgroup whose segment(s) are empty returns before it forms a tile.  The
 //                 tile (with ORIENT: both tiles) is parked in LDS over the dead image, 64 rows of 68 floats each, and the
@@ -23,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <type_traits>
 
 #include "../../include/phoenix_hip.h"
 #include "phx_host.hpp"
@@ -31,33 +33,15 @@ namespace {
 
 #include "phx_effects_tile.inc"
 
-constexpr int NSC_TLD = 68;                          // floats of a row of a parked tile
-constexpr int NSC_TBUF = EFX_TILE * NSC_TLD;         // 4352 floats
-constexpr unsigned NSC_INF = 0x7f800000u;            // m < NSC_INF: finite;  m <= NSC_INF: not a NaN
 constexpr unsigned NSC_NAN = 0x7fc00000u;            // GATHER: a key outside the tile of its segment
 constexpr size_t NSC_WS_BYTES = 64;                  // unsigned nonfinite at byte 0, padding
 constexpr unsigned NSC_MAX_M = 0x7fffffffu;          // 2 m + 1 fits 32 bits
-
-__device__ __forceinline__ void nsc_tile_of_block(bool orient, int T, int &I, int &J)
-{
-    if (orient) {
-        // blockIdx.x = J (J + 1) / 2 + I with I <= J: the root by float, then made exact
-        const int p = blockIdx.x;
-        J = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
-        while ((J + 1) * (J + 2) / 2 <= p) ++J;
-        while (J * (J + 1) / 2 > p) --J;
-        I = p - J * (J + 1) / 2;
-    } else {
-        I = blockIdx.x / T;
-        J = blockIdx.x - I * T;
-    }
-}
 
 // the masked value of `a` against its partner `b`: make_mask keeps a only when |a| > |b| (false with a NaN on either side)
 __device__ __forceinline__ float nsc_masked(float a, float b)
 {
     const unsigned ma = __float_as_uint(a) & 0x7fffffffu, mb = __float_as_uint(b) & 0x7fffffffu;
-    return (ma <= NSC_INF && mb <= NSC_INF && ma > mb) ? a : 0.f;
+    return (ma <= EFX_INF && mb <= EFX_INF && ma > mb) ? a : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------- GATHER
@@ -75,7 +59,7 @@ __global__ __launch_bounds__(EFX_THREADS) void k_gather(const float *__restrict_
     const int iw = (wv & 1) * 32, jw = (wv >> 1) * 32;
     const int T = (N + EFX_TILE - 1) / EFX_TILE;
     int I, J;
-    nsc_tile_of_block(ORIENT, T, I, J);
+    efx_tile_of_block(ORIENT, T, I, J);
     // the segments of tile (I, J) and, with ORIENT, of tile (J, I); offsets are clamped to the list
     unsigned fb = min(off[I * T + J], n_keys), fe = min(off[I * T + J + 1], n_keys);
     unsigned rb = 0, re = 0;
@@ -92,16 +76,10 @@ __global__ __launch_bounds__(EFX_THREADS) void k_gather(const float *__restrict_
     if (ORIENT && I != J) {
         __syncthreads();                       // every wave is done with the image of tile (I, J)
         efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, j0, i0, vb);
-        tb = lds + NSC_TBUF;
+        tb = lds + EFX_TBUF;
     }
     __syncthreads();                           // the image is dead: the parked tiles take its place
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 2; ++tj) {
-            *reinterpret_cast<f4 *>(ta + (iw + 16 * ti + lc) * NSC_TLD + jw + 16 * tj + 4 * lq) = va[ti][tj];
-            if (ORIENT && I != J) *reinterpret_cast<f4 *>(tb + (iw + 16 * ti + lc) * NSC_TLD + jw + 16 * tj + 4 * lq) = vb[ti][tj];
-        }
+    efx_park(ta, va, tb, vb, ORIENT && I != J, iw + lc, jw + 4 * lq);
     __syncthreads();
 
     for (unsigned n = fb + tid; n < fe; n += EFX_THREADS) {
@@ -109,8 +87,8 @@ __global__ __launch_bounds__(EFX_THREADS) void k_gather(const float *__restrict_
         const unsigned il = i - (unsigned)i0, jl = j - (unsigned)j0;
         float v = __uint_as_float(NSC_NAN);
         if (il < (unsigned)EFX_TILE && jl < (unsigned)EFX_TILE) {
-            v = ta[il * NSC_TLD + jl];
-            if (ORIENT) v = i == j ? 0.f : nsc_masked(v, tb[jl * NSC_TLD + il]);
+            v = ta[il * EFX_TLD + jl];
+            if (ORIENT) v = i == j ? 0.f : nsc_masked(v, tb[jl * EFX_TLD + il]);
         }
         values[n] = v;
     }
@@ -118,7 +96,7 @@ __global__ __launch_bounds__(EFX_THREADS) void k_gather(const float *__restrict_
         const unsigned key = keys[n], j = key / (unsigned)N, i = key - j * (unsigned)N;
         const unsigned il = i - (unsigned)i0, jl = j - (unsigned)j0;
         float v = __uint_as_float(NSC_NAN);
-        if (il < (unsigned)EFX_TILE && jl < (unsigned)EFX_TILE) v = nsc_masked(tb[jl * NSC_TLD + il], ta[il * NSC_TLD + jl]);
+        if (il < (unsigned)EFX_TILE && jl < (unsigned)EFX_TILE) v = nsc_masked(tb[jl * EFX_TLD + il], ta[il * EFX_TLD + jl]);
         values[n] = v;
     }
 }
@@ -151,7 +129,7 @@ __device__ __forceinline__ void nsc_rank16(const unsigned (&x)[16], unsigned val
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         if (!((valid >> e) & 1u)) continue;
-        if (x[e] >= NSC_INF) {
+        if (x[e] >= EFX_INF) {
             ++hot[4];
             continue;
         }
@@ -178,39 +156,20 @@ __global__ __launch_bounds__(EFX_THREADS) void k_rank(const float *__restrict__ 
     const int iw = (wv & 1) * 32, jw = (wv >> 1) * 32;
     const int T = (N + EFX_TILE - 1) / EFX_TILE;
     int I, J;
-    nsc_tile_of_block(ORIENT, T, I, J);
+    efx_tile_of_block(ORIENT, T, I, J);
     const int i0 = I * EFX_TILE, j0 = J * EFX_TILE;
 
     f4 va[2][2];                   // tile (I, J)
     f4 vp[2][2];                   // ORIENT: vp[ti][tj][r] = M[j, i] for the entry (i, j) of va[ti][tj][r]
-    efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, i0, j0, va);
+    const auto zero_hot = [&] {
+        if (tid < 5) wg_hot[tid] = 0;
+    };
     if (ORIENT) {
-        f4 vb[2][2];               // tile (J, I)
-        if (I != J) {
-            __syncthreads();       // every wave is done with the image of tile (I, J)
-            efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, j0, i0, vb);
-        } else {
-#pragma unroll
-            for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-                for (int tj = 0; tj < 2; ++tj) vb[ti][tj] = va[ti][tj];
-        }
-        __syncthreads();           // the image is dead: the transposed tile takes its place
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-                *reinterpret_cast<f4 *>(lds + (iw + 16 * ti + lc) * NSC_TLD + jw + 16 * tj + 4 * lq) = vb[ti][tj];
-    }
-    if (tid < 5) wg_hot[tid] = 0;
-    __syncthreads();
-    if (ORIENT) {
-#pragma unroll
-        for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-            for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) vp[ti][tj][r] = lds[(jw + 16 * tj + 4 * lq + r) * NSC_TLD + iw + 16 * ti + lc];
+        efx_tile_pair<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, I, J, iw + lc, jw + 4 * lq, va, vp, zero_hot);
+    } else {
+        efx_tile<MODE>(lds, Ws, Wp, WaT, g, y, ph, N, H, B, i0, j0, va);
+        zero_hot();
+        __syncthreads();
     }
 
     // the scores of this lane's entries: bit 4 (2 ti + tj) + r of `fwd` for (i, j), of `rev` for (j, i)
@@ -230,7 +189,7 @@ __global__ __launch_bounds__(EFX_THREADS) void k_rank(const float *__restrict__ 
                 if (inside && (i != j || a.diagonal)) fwd |= 1u << e;
                 if (ORIENT) {
                     const unsigned mb = __float_as_uint(vp[ti][tj][r]) & 0x7fffffffu;
-                    const bool cmp = ma <= NSC_INF && mb <= NSC_INF;
+                    const bool cmp = ma <= EFX_INF && mb <= EFX_INF;
                     xf[e] = (cmp && ma > mb && i != j) ? ma : 0u;
                     xr[e] = (cmp && mb > ma) ? mb : 0u;
                     if (inside && I != J) rev |= 1u << e;
@@ -259,14 +218,9 @@ __global__ __launch_bounds__(EFX_THREADS) void k_rank(const float *__restrict__ 
     }
 }
 
-// i N + j must fit the 32 bits of a key, N^2 the 32 bits of a count
-bool netscore_shape_ok(int N, int H) { return effects_shape_ok(N, H) && N <= 65535; }
-
-bool netscore_mode_ok(int mode) { return mode == PHX_EFFECTS || mode == PHX_JAC_MEAN || mode == PHX_JAC_MEAN_ABS; }
-
 size_t netscore_lds_bytes(int H, int mode, int tiles)
 {
-    const size_t tile = effects_lds_bytes(H, mode), tail = (size_t)tiles * NSC_TBUF * sizeof(float);
+    const size_t tile = effects_lds_bytes(H, mode), tail = (size_t)tiles * EFX_TBUF * sizeof(float);
     return tile > tail ? tile : tail;
 }
 
@@ -276,19 +230,9 @@ int gather_launch(const phx_params *p, const float *y, const float *ph, int B, c
 {
     const size_t lds = netscore_lds_bytes(p->H, MODE, ORIENT ? 2 : 1);
     if (!phxh::set_lds(k_gather<MODE, ORIENT>, lds)) return PHX_ERR_LAUNCH;
-    const int T = (p->N + EFX_TILE - 1) / EFX_TILE;
-    const dim3 grid(ORIENT ? T * (T + 1) / 2 : T * T);
-    hipLaunchKernelGGL((k_gather<MODE, ORIENT>), grid, dim3(EFX_THREADS), lds, st, p->Ws, p->Wp, p->WaT, p->g, y, ph, p->N,
-                       p->H, B, keys, off, n_keys, values);
+    hipLaunchKernelGGL((k_gather<MODE, ORIENT>), dim3(efx_pair_grid(p->N, ORIENT)), dim3(EFX_THREADS), lds, st, p->Ws, p->Wp,
+                       p->WaT, p->g, y, ph, p->N, p->H, B, keys, off, n_keys, values);
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
-}
-
-template <int MODE>
-int gather_launch(const phx_params *p, const float *y, const float *ph, int B, bool orient, const unsigned *keys,
-                  const unsigned *off, unsigned n_keys, float *values, hipStream_t st)
-{
-    return orient ? gather_launch<MODE, true>(p, y, ph, B, keys, off, n_keys, values, st)
-                  : gather_launch<MODE, false>(p, y, ph, B, keys, off, n_keys, values, st);
 }
 
 template <int MODE, bool ORIENT>
@@ -296,25 +240,9 @@ int rank_launch(const phx_params *p, const float *y, const float *ph, int B, con
 {
     const size_t lds = netscore_lds_bytes(p->H, MODE, ORIENT ? 1 : 0);
     if (!phxh::set_lds(k_rank<MODE, ORIENT>, lds)) return PHX_ERR_LAUNCH;
-    const int T = (p->N + EFX_TILE - 1) / EFX_TILE;
-    const dim3 grid(ORIENT ? T * (T + 1) / 2 : T * T);
-    hipLaunchKernelGGL((k_rank<MODE, ORIENT>), grid, dim3(EFX_THREADS), lds, st, p->Ws, p->Wp, p->WaT, p->g, y, ph, p->N, p->H,
-                       B, a);
+    hipLaunchKernelGGL((k_rank<MODE, ORIENT>), dim3(efx_pair_grid(p->N, ORIENT)), dim3(EFX_THREADS), lds, st, p->Ws, p->Wp,
+                       p->WaT, p->g, y, ph, p->N, p->H, B, a);
     return hipGetLastError() == hipSuccess ? PHX_OK : PHX_ERR_LAUNCH;
-}
-
-template <int MODE>
-int rank_launch(const phx_params *p, const float *y, const float *ph, int B, bool orient, const rank_args &a, hipStream_t st)
-{
-    return orient ? rank_launch<MODE, true>(p, y, ph, B, a, st) : rank_launch<MODE, false>(p, y, ph, B, a, st);
-}
-
-bool netscore_args_ok(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags)
-{
-    if (!p || !p->Ws || !p->Wp || !p->WaT || !p->g || !netscore_shape_ok(p->N, p->H)) return false;
-    if (!netscore_mode_ok(mode)) return false;
-    if (mode != PHX_EFFECTS && (!y || !ph || B < 1)) return false;
-    return !(flags & ~(PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL));
 }
 
 }  // namespace
@@ -323,7 +251,8 @@ extern "C" {
 
 size_t phx_effects_rank_workspace_bytes(int N, int H, int B, int mode)
 {
-    if (!netscore_shape_ok(N, H) || !netscore_mode_ok(mode)) return 0;
+    // i N + j must fit the 32 bits of a key, N^2 the 32 bits of a count
+    if (!efx_pair_shape_ok(N, H) || !efx_mode_ok(mode)) return 0;
     if (mode != PHX_EFFECTS && B < 1) return 0;
     return NSC_WS_BYTES;
 }
@@ -331,21 +260,22 @@ size_t phx_effects_rank_workspace_bytes(int N, int H, int B, int mode)
 int phx_effects_gather(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, const unsigned *keys,
                        const unsigned *tile_offsets, unsigned n_keys, float *values, void *stream)
 {
-    if (!netscore_args_ok(p, mode, y, ph, B, flags)) return PHX_ERR_BAD_ARG;
+    if (!efx_args_ok(p, mode, y, ph, B, flags, PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_pair_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
     if (!keys || !tile_offsets || !values || n_keys < 1) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const bool orient = (flags & PHX_EDGES_ORIENT) != 0;
-    switch (mode) {
-    case PHX_EFFECTS: return gather_launch<PHX_EFFECTS>(p, nullptr, nullptr, 1, orient, keys, tile_offsets, n_keys, values, st);
-    case PHX_JAC_MEAN: return gather_launch<PHX_JAC_MEAN>(p, y, ph, B, orient, keys, tile_offsets, n_keys, values, st);
-    default: return gather_launch<PHX_JAC_MEAN_ABS>(p, y, ph, B, orient, keys, tile_offsets, n_keys, values, st);
-    }
+    return efx_dispatch(mode, (flags & PHX_EDGES_ORIENT) != 0, y, ph, B,
+                        [&](auto MODE, auto ORIENT, const float *ys, const float *phs, int Bs) {
+                            return gather_launch<decltype(MODE)::value, decltype(ORIENT)::value>(p, ys, phs, Bs, keys,
+                                                                                                 tile_offsets, n_keys, values, st);
+                        });
 }
 
 int phx_effects_rank_counts(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, const unsigned *u,
                             unsigned m, unsigned *counts, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!netscore_args_ok(p, mode, y, ph, B, flags)) return PHX_ERR_BAD_ARG;
+    if (!efx_args_ok(p, mode, y, ph, B, flags, PHX_EDGES_ORIENT | PHX_EDGES_DIAGONAL)) return PHX_ERR_BAD_ARG;
+    if (!efx_pair_shape_ok(p->N, p->H)) return PHX_ERR_BAD_ARG;
     if (!u || !counts || m < 1 || m > NSC_MAX_M) return PHX_ERR_BAD_ARG;
     const size_t need = phx_effects_rank_workspace_bytes(p->N, p->H, B, mode);
     if (!workspace || workspace_bytes < need) return PHX_ERR_WORKSPACE;
@@ -360,12 +290,10 @@ int phx_effects_rank_counts(const phx_params *p, int mode, const float *y, const
     a.diagonal = (flags & PHX_EDGES_DIAGONAL) != 0;
     if (hipMemsetAsync(counts, 0, (2 * (size_t)m + 1) * sizeof(unsigned), st) != hipSuccess) return PHX_ERR_LAUNCH;
     if (hipMemsetAsync(a.nonfinite, 0, sizeof(unsigned), st) != hipSuccess) return PHX_ERR_LAUNCH;
-    const bool orient = (flags & PHX_EDGES_ORIENT) != 0;
-    switch (mode) {
-    case PHX_EFFECTS: return rank_launch<PHX_EFFECTS>(p, nullptr, nullptr, 1, orient, a, st);
-    case PHX_JAC_MEAN: return rank_launch<PHX_JAC_MEAN>(p, y, ph, B, orient, a, st);
-    default: return rank_launch<PHX_JAC_MEAN_ABS>(p, y, ph, B, orient, a, st);
-    }
+    return efx_dispatch(mode, (flags & PHX_EDGES_ORIENT) != 0, y, ph, B,
+                        [&](auto MODE, auto ORIENT, const float *ys, const float *phs, int Bs) {
+                            return rank_launch<decltype(MODE)::value, decltype(ORIENT)::value>(p, ys, phs, Bs, a, st);
+                        });
 }
 
 }  // extern "C"

@@ -102,6 +102,16 @@ def _workspace(op, N, H, B, T, device, calls=1, grids_method=None):
     return buf, nbytes
 
 
+def _analysis_workspace(op, nbytes, device):
+    """the cached uint8 workspace of the analysis op `op` on the current stream of `device`, at least `nbytes` long (the
+    callers that read counters from it view it as int32)"""
+    key = (device.index, _stream_raw(device.index), op)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=device)
+    return ws
+
+
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
@@ -642,29 +652,48 @@ def _require_f32(x, name):
         raise TypeError("phoenix_amd: `%s` must be float32 (got %s)" % (name, x.dtype))
 
 
+def _effects_states(name, params, mode, y, ph, pairs):
+    """(y, ph, B) of a call on the effects tile engine, checked: the mode, with `pairs` the shapes whose gene pairs fit the
+    32-bit keys of the selecting kernels, and for the Jacobian modes the states y [B, N] and ph [B, H]"""
+    if mode not in _lib.EFFECTS_MODES:
+        raise ValueError("%s: mode must be one of %s, got %r" % (name, sorted(_lib.EFFECTS_MODES), mode))
+    N, H = params.N, params.H
+    if pairs and (H > 256 or N > 65535):
+        raise ValueError("%s: H <= 256 and N <= 65535 are served, got N=%d, H=%d" % (name, N, H))
+    if mode == "effects":
+        return None, None, 1
+    if y is None or ph is None:
+        raise ValueError("%s: mode %r needs the states `y` [B, N] and `ph` [B, H]" % (name, mode))
+    _require_f32(y, "y")
+    _require_f32(ph, "ph")
+    B = y.shape[0] if y.dim() == 2 else 0
+    if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
+            y.device != params.device or ph.device != params.device:
+        raise ValueError("%s: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
+                         "parameters' device, got %s and %s" % (name, N, H, tuple(y.shape), tuple(ph.shape)))
+    return y, ph, B
+
+
+def _edges_flags(orient, diagonal):
+    return (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
+
+
+def _check_threshold(name, threshold):
+    """ValueError unless `threshold` is None or a positive, finite number"""
+    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and
+                                      not isinstance(threshold, bool) and threshold > 0 and np.isfinite(threshold)):
+        raise ValueError("%s: threshold must be positive and finite, got %r" % (name, threshold))
+
+
 def effects_matrix(params, mode, y=None, ph=None, rows=None, out=None):
     """phx_effects_matrix on laid-out parameters (`Params`): rows [row0, row1) of the regulator -> target matrix of `mode`
     ("effects": extract_model_matrix_PHOENIX.py:46-58; "mean" / "mean_abs": the RHS Jacobian averaged over the states
     y [B, N] as it is / in absolute value, with ph [B, H] the product-branch hidden vector of those states) -> float32
     [row1 - row0, N] on the device.  `rows`: None (all N) or (row0, row1).  `out`: a contiguous float32 device tensor of
     that shape to write into instead of a fresh one."""
-    if mode not in _lib.EFFECTS_MODES:
-        raise ValueError("effects_matrix: mode must be one of %s, got %r" % (sorted(_lib.EFFECTS_MODES), mode))
     N, H = params.N, params.H
     row0, row1 = check_rows(rows, N)
-    B = 1
-    if mode != "effects":
-        if y is None or ph is None:
-            raise ValueError("effects_matrix: mode %r needs the states `y` [B, N] and `ph` [B, H]" % mode)
-        _require_f32(y, "y")
-        _require_f32(ph, "ph")
-        B = y.shape[0] if y.dim() == 2 else 0
-        if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
-                y.device != params.device or ph.device != params.device:
-            raise ValueError("effects_matrix: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
-                             "parameters' device, got %s and %s" % (N, H, tuple(y.shape), tuple(ph.shape)))
-    else:
-        y = ph = None
+    y, ph, B = _effects_states("effects_matrix", params, mode, y, ph, pairs=False)
     if out is None:
         out = torch.empty((row1 - row0, N), dtype=torch.float32, device=params.device)
     else:
@@ -676,12 +705,7 @@ def effects_matrix(params, mode, y=None, ph=None, rows=None, out=None):
     nbytes = _ws_bytes.get(key)
     if nbytes is None:
         nbytes = _ws_bytes[key] = _lib.load().phx_effects_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode])
-    ws = None
-    if nbytes:
-        key = (params.device.index, _stream_raw(params.device.index), OP_EFFECTS)
-        ws = _ws_cache.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=params.device)
+    ws = _analysis_workspace(OP_EFFECTS, nbytes, params.device) if nbytes else None
     p = params.on_current_stream()
     _check_call(_lib.load().phx_effects_matrix(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, row0, row1, _p(out),
                                                _p(ws), nbytes, _stream_ptr()))
@@ -715,9 +739,7 @@ def check_edges_selection(top, threshold, max_edges):
         raise ValueError("effects_edges: exactly one of `top` and `threshold` must be given")
     if top is not None and (not _is_int(top) or top < 1):
         raise ValueError("effects_edges: top must be an integer >= 1, got %r" % (top,))
-    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and
-                                      not isinstance(threshold, bool) and threshold > 0 and np.isfinite(threshold)):
-        raise ValueError("effects_edges: threshold must be positive and finite, got %r" % (threshold,))
+    _check_threshold("effects_edges", threshold)
     if max_edges is not None:
         if threshold is None:
             raise ValueError("effects_edges: max_edges applies to `threshold` only")
@@ -736,34 +758,14 @@ def effects_edges(params, mode, y=None, ph=None, top=None, threshold=None, orien
     a list of that capacity; RuntimeError with the true count when more entries qualify.  `refine_above`: the cap on the
     entries of the cut bin (default max(4 top, 2^20)): a fuller bin is refined once on its next 12 bits, and `top` raises
     RuntimeError when the refined cut bin is still fuller."""
-    if mode not in _lib.EFFECTS_MODES:
-        raise ValueError("effects_edges: mode must be one of %s, got %r" % (sorted(_lib.EFFECTS_MODES), mode))
     check_edges_selection(top, threshold, max_edges)
-    N, H = params.N, params.H
-    if H > 256 or N > 65535:
-        raise ValueError("effects_edges: H <= 256 and N <= 65535 are served, got N=%d, H=%d" % (N, H))
-    B = 1
-    if mode != "effects":
-        if y is None or ph is None:
-            raise ValueError("effects_edges: mode %r needs the states `y` [B, N] and `ph` [B, H]" % mode)
-        _require_f32(y, "y")
-        _require_f32(ph, "ph")
-        B = y.shape[0] if y.dim() == 2 else 0
-        if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
-                y.device != params.device or ph.device != params.device:
-            raise ValueError("effects_edges: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
-                             "parameters' device, got %s and %s" % (N, H, tuple(y.shape), tuple(ph.shape)))
-    else:
-        y = ph = None
-    dev = params.device
+    y, ph, B = _effects_states("effects_edges", params, mode, y, ph, pairs=True)
+    N, H, dev = params.N, params.H, params.device
     lib = _lib.load()
     nbytes = lib.phx_effects_edges_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode])
-    key = (dev.index, _stream_raw(dev.index), OP_EDGES)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _ws_cache[key] = torch.empty(int(nbytes) // 4 + 16, dtype=torch.int32, device=dev)
+    ws = _analysis_workspace(OP_EDGES, nbytes, dev).view(torch.int32)      # the histogram, then the cursor
     p = params.on_current_stream()
-    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
+    flags = _edges_flags(orient, diagonal)
 
     def run(pass_, level=0, prefix=0, tau=0.0, keys=None, values=None):
         _check_call(lib.phx_effects_edges(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, pass_, level,
@@ -866,9 +868,7 @@ def check_neighbors_selection(k, of, regulators, targets, threshold, N):
         raise ValueError("%s: k must be an integer in [1, %d], got %r" % (name, _lib.NEIGHBORS_MAX_K, k))
     if not isinstance(of, str) or of not in _lib.NEIGHBORS_AXES:
         raise ValueError('%s: of must be "target" or "regulator", got %r' % (name, of))
-    if threshold is not None and not (isinstance(threshold, (int, float, np.integer, np.floating)) and
-                                      not isinstance(threshold, bool) and threshold > 0 and np.isfinite(threshold)):
-        raise ValueError("%s: threshold must be positive and finite, got %r" % (name, threshold))
+    _check_threshold(name, threshold)
     return int(k), _lib.NEIGHBORS_AXES[of], _gene_set(name, "regulators", regulators, N), _gene_set(name, "targets", targets, N)
 
 
@@ -880,7 +880,7 @@ def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=
     device.  `regulators` / `targets`: candidate gene indices (None: all), turned into byte masks on the device.  One call:
     the matrix is not formed."""
     k, axis, regulators, targets = check_neighbors_selection(k, of, regulators, targets, threshold, params.N)
-    y, ph, B = _netscore_states("effects_neighbors", params, mode, y, ph)
+    y, ph, B = _effects_states("effects_neighbors", params, mode, y, ph, pairs=True)
     N, H, dev = params.N, params.H, params.device
     tau = 0.0
     if threshold is not None:
@@ -898,17 +898,14 @@ def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=
             masks.append(m)
     lib = _lib.load()
     nbytes = lib.phx_effects_neighbors_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode], axis, k)
-    wkey = (dev.index, _stream_raw(dev.index), OP_NEIGHBORS)
-    ws = _ws_cache.get(wkey)
-    if ws is None or ws.numel() < nbytes:
-        ws = _ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    ws = _analysis_workspace(OP_NEIGHBORS, nbytes, dev)
     gene = torch.empty((N, k), dtype=torch.int32, device=dev)
     value = torch.empty((N, k), dtype=torch.float32, device=dev)
     count = torch.empty(N, dtype=torch.int32, device=dev)
     strength = torch.empty(N, dtype=torch.float32, device=dev)
     p = params.on_current_stream()
-    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
-    _check_call(lib.phx_effects_neighbors(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, axis, k, tau,
+    _check_call(lib.phx_effects_neighbors(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B,
+                                          _edges_flags(orient, diagonal), axis, k, tau,
                                           _p(masks[0]), _p(masks[1]), _p(gene), _p(value), _p(count), _p(strength), _p(ws),
                                           nbytes, _stream_ptr()))
     return gene.to(torch.int64), value, count.to(torch.int64), strength
@@ -976,10 +973,7 @@ def pathway_permutations(scores, ptr, idx, seed, first, n_perm):
     s_idx = idx[torch.repeat_interleave(ptr[:-1][order], s_sizes) + within].to(torch.int32)
     lib = _lib.load()
     nbytes = lib.phx_pathway_permutations_workspace_bytes(N, P, nnz, n_perm)
-    wkey = (dev.index, _stream_raw(dev.index), OP_PATHWAYS)
-    ws = _ws_cache.get(wkey)
-    if ws is None or ws.numel() < nbytes:
-        ws = _ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=dev)
+    ws = _analysis_workspace(OP_PATHWAYS, nbytes, dev)
     base = torch.empty(P, dtype=torch.float64, device=dev)
     count = torch.empty(P, dtype=torch.int64, device=dev)
     s1 = torch.empty(P, dtype=torch.float64, device=dev)
@@ -993,27 +987,6 @@ def pathway_permutations(scores, ptr, idx, seed, first, n_perm):
 
 OP_NETSCORE = 8      # workspace-cache key of network_score (phx_effects_rank_workspace_bytes sizes it)
 NETSCORE_TILE = 64  # the tile by which phx_effects_gather wants its keys grouped
-
-
-def _netscore_states(name, params, mode, y, ph):
-    """(y, ph, B) of the scoring calls, checked as `effects_edges` checks them"""
-    if mode not in _lib.EFFECTS_MODES:
-        raise ValueError("%s: mode must be one of %s, got %r" % (name, sorted(_lib.EFFECTS_MODES), mode))
-    N, H = params.N, params.H
-    if H > 256 or N > 65535:
-        raise ValueError("%s: H <= 256 and N <= 65535 are served, got N=%d, H=%d" % (name, N, H))
-    if mode == "effects":
-        return None, None, 1
-    if y is None or ph is None:
-        raise ValueError("%s: mode %r needs the states `y` [B, N] and `ph` [B, H]" % (name, mode))
-    _require_f32(y, "y")
-    _require_f32(ph, "ph")
-    B = y.shape[0] if y.dim() == 2 else 0
-    if B < 1 or y.shape[1] != N or tuple(ph.shape) != (B, H) or not y.is_contiguous() or not ph.is_contiguous() or \
-            y.device != params.device or ph.device != params.device:
-        raise ValueError("%s: y must be a contiguous [B, %d] and ph a contiguous [B, %d] tensor on the "
-                         "parameters' device, got %s and %s" % (name, N, H, tuple(y.shape), tuple(ph.shape)))
-    return y, ph, B
 
 
 def check_network_indices(name, regulator, target, N):
@@ -1053,7 +1026,7 @@ def effects_gather(params, mode, regulator, target, y=None, ph=None, orient=Fals
     make_mask form (include/phoenix_hip.h).  regulator, target: int64 tensors [E] on the parameters' device with values in
     [0, N) (check_network_indices); duplicates are allowed.  The keys are grouped by tile with one sort; only the tiles
     that hold a listed entry are formed."""
-    y, ph, B = _netscore_states("effects_at", params, mode, y, ph)
+    y, ph, B = _effects_states("effects_at", params, mode, y, ph, pairs=True)
     N, dev = params.N, params.device
     E = regulator.numel()
     if E == 0:
@@ -1069,7 +1042,7 @@ def effects_gather(params, mode, regulator, target, y=None, ph=None, orient=Fals
     sorted_values = torch.empty(E, dtype=torch.float32, device=dev)
     p = params.on_current_stream()
     _check_call(_lib.load().phx_effects_gather(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B,
-                                               _lib.EDGES_ORIENT if orient else 0, _p(keys), _p(offsets), E, _p(sorted_values),
+                                               _edges_flags(orient, False), _p(keys), _p(offsets), E, _p(sorted_values),
                                                _stream_ptr()))
     values = torch.empty_like(sorted_values)
     values[order] = sorted_values
@@ -1084,7 +1057,7 @@ def network_score(params, mode, regulator, target, y=None, ph=None, orient=False
     positives' values, a sort makes the distinct magnitudes u and their multiplicities, RANK counts every scored entry
     between and on them, and cumulative sums of the 2 m + 1 counts are the curve.  Everything is integer arithmetic up to
     the two final float64 divisions."""
-    y, ph, B = _netscore_states("network_score", params, mode, y, ph)
+    y, ph, B = _effects_states("network_score", params, mode, y, ph, pairs=True)
     N, dev = params.N, params.device
     key = torch.unique(regulator * N + target)
     if not diagonal:
@@ -1102,15 +1075,12 @@ def network_score(params, mode, regulator, target, y=None, ph=None, orient=False
     m = int(u.numel())
     lib = _lib.load()
     nbytes = lib.phx_effects_rank_workspace_bytes(N, params.H, B, _lib.EFFECTS_MODES[mode])
-    wkey = (dev.index, _stream_raw(dev.index), OP_NETSCORE)
-    ws = _ws_cache.get(wkey)
-    if ws is None or ws.numel() * 4 < nbytes:
-        ws = _ws_cache[wkey] = torch.empty(int(nbytes) // 4 + 16, dtype=torch.int32, device=dev)
+    ws = _analysis_workspace(OP_NETSCORE, nbytes, dev).view(torch.int32)    # the count of non-finite entries first
     counts = torch.empty(2 * m + 1, dtype=torch.int32, device=dev)
     p = params.on_current_stream()
-    flags = (_lib.EDGES_ORIENT if orient else 0) | (_lib.EDGES_DIAGONAL if diagonal else 0)
-    _check_call(lib.phx_effects_rank_counts(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, flags, _p(u), m,
-                                            _p(counts), _p(ws), nbytes, _stream_ptr()))
+    _check_call(lib.phx_effects_rank_counts(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B,
+                                            _edges_flags(orient, diagonal), _p(u), m, _p(counts), _p(ws), nbytes,
+                                            _stream_ptr()))
     bad = int(ws[0].item()) & 0xFFFFFFFF
     if bad:
         raise ValueError("network_score: %d scored entries are not finite" % bad)
