@@ -498,6 +498,18 @@ int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, in
 int phx_debug_calls_grids_kernel_m(int N, int H, int B, int T, int calls, int method);
 int phx_debug_calls_grids_plan(int N, int H, int B, int T, int calls, int method, int *plan);
 int phx_debug_calls_grids_launches(int N, int H, int B, int T, int calls, int method);
+/* Diagnostic only, needs no device: the plan of ONE launch of B rows by the solve kernel `kernel_id` of direction `op`
+ * (PHX_OP_ODEINT: 1, 3, 4; PHX_OP_ADJOINT: 1 .. 4 and 5 = k1_solve_bp) on a device of `cus` compute units; calls > 1
+ * (forward kernels): the rows are that many shared-control calls of B / calls rows.  Returns 0 where that kernel does
+ * not plan the shape, else PHX_DEBUG_PLAN_FIELDS after writing out[0 .. PHX_DEBUG_PLAN_FIELDS - 1] =
+ *   the launch geometry  N, H, B, T, HT, NB, NW, TPW, G, TG, nblk, ntg, Bt, nvec, BN, HC, Hc, Bcall, cntN, res, hb, split,
+ *   the workspace layout (with gradients)  total, then the byte offsets cnt, part, zbuf, part1, zbuf1, scratch, dtheta,
+ *     prof, wimg, hq, then xbytes (what a fill covers from `part` on), pp (floats per gradient partial), nparts,
+ *   and the dynamic LDS bytes of the launch.
+ * A planner change shows as the values it moves (tools/plan_table.py --cus, tests/golden/solve_plans.txt). */
+#define PHX_DEBUG_PLAN_FIELDS 37
+int phx_debug_plan(int op, int kernel_id, int cus, int N, int H, int B, int T, int control, int method, int calls,
+                   long long *out);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_backprop_workspace_bytes", "phx_debug_backprop_kernel_m", "phx_debug_backprop_launches",
            "phx_debug_backprop_plan",
            "phx_odeint_calls_grids_workspace_bytes", "phx_debug_calls_grids_kernel_m", "phx_debug_calls_grids_plan",
-           "phx_debug_calls_grids_launches", "phx_influence_workspace_bytes", "phx_influence_scores",
+           "phx_debug_calls_grids_launches", "phx_debug_plan", "phx_influence_workspace_bytes", "phx_influence_scores",
            "phx_effects_workspace_bytes", "phx_effects_matrix", "phx_effects_edges_workspace_bytes", "phx_effects_edges",
            "phx_effects_rank_workspace_bytes", "phx_effects_gather", "phx_effects_rank_counts",
            "phx_effects_neighbors_workspace_bytes", "phx_effects_neighbors", "phx_pathway_permutations_workspace_bytes",
@@ -122,6 +122,7 @@ def load():
     lib.phx_debug_calls_grids_kernel_m.argtypes = [C.c_int] * 6
     lib.phx_debug_calls_grids_plan.argtypes = [C.c_int] * 6 + [C.POINTER(C.c_int)]
     lib.phx_debug_calls_grids_launches.argtypes = [C.c_int] * 6
+    lib.phx_debug_plan.argtypes = [C.c_int] * 10 + [C.POINTER(C.c_longlong)]
     lib.phx_weight_image_bytes.argtypes = [C.c_int, C.c_int]
     lib.phx_weight_image_bytes.restype = C.c_size_t
     lib.phx_pack_weight_images.argtypes = [C.POINTER(PhxParams), vp, vp]

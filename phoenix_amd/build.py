@@ -64,7 +64,7 @@ def listing_of(src):
     return os.path.join(OBJ, os.path.basename(src)[:-4] + ".s")
 
 
-def _keep_listing(src, dst, stem=None):
+def _keep_listing(src, dst):
     """moves the gfx950 assembly `-save-temps=obj` left beside the object to `dst` and deletes the other temporaries"""
     # (the temporaries are named after the SOURCE file, whatever the object is called)
     stem = os.path.basename(src)[:-4]

@@ -773,6 +773,7 @@ PHX_V1_ADJ(8, 256, false);
 #include "phx_mfma_batch.inc"
 #include "phx_prior.inc"
 #include "phx_hill.inc"
+#include "phx_plan.hpp"
 
 // ========================================================================================
 // host side: C ABI
@@ -780,6 +781,12 @@ PHX_V1_ADJ(8, 256, false);
 namespace {
 
 
+
+// gradients wanted, but a pointer of them is missing (Wa in either layout)
+inline bool bad_grads(const phx_grads *g)
+{
+    return g && (!g->Ws || !g->bs || !g->Wp || !g->bp || (!g->WaT && !g->Wa) || !g->g);
+}
 
 inline bool bad_params(const phx_params *p)
 {
@@ -802,163 +809,56 @@ inline int launch_reduce(const Dims &d, const WS &w, const phx_grads *g, hipStre
 // ---------------------------------------------------------------------------------------------------
 // v1 (MFMA) launch planning
 // ---------------------------------------------------------------------------------------------------
-constexpr size_t ADJ_LDS_EXTRA = 0;
-constexpr int ADJ_NW_CAP = 4;   // the augmented kernel needs the 512-register budget of one wave per SIMD
-
 
 // hidden-fragment tiles of the solve kernels: 3 for a narrow hidden layer, 8 (128 rows) otherwise -- except for a chunked
 // hidden layer whose chunks need only 7 tiles (96 < Hc <= 112; the B-cell shape: H = 200 -> 2 x 100), where the eighth
 // tile would be 12.5 % of the MFMAs, exchange rows and quadrature accumulators spent on padding
 inline int solve_ht(int HC, int Hc) { return Hc <= 48 ? 3 : ((HC > 1 && Hc <= 112) ? 7 : 8); }
 
-// picks (NW, TPW, NB): minimise the per-wave MFMA work TPW*NB subject to LDS and residency
-bool plan_v1(int N, int H, int B, int T, int control, int nvec, int fwidth /* hidden frag tiles / HT */,
-             size_t lds_per_block_extra, D1 *out, size_t ctl_extra_per_traj = 0, int nw_cap = 8, int calls = 1,
-             int cus_given = 0 /* > 0: plan for this many CUs instead of the current device's */)
+// plan_resident for k1_solve_fwd / k1_solve_adj (any method).  H > 128: the hidden layer is cut into HC chunks of
+// Hc <= 128 rows whose weights take turns in LDS.  nw_cap: up to eight waves forward (two per SIMD: latency hiding, and
+// the cost prefers them); the augmented kernel needs the 512-register budget of one wave per SIMD -- and with HT = 3 the
+// kernel's LDS combine layout relies on NW <= 4.  ctl_per_traj: control LDS per trajectory beside ctl_bytes.
+bool plan_v1(const Shape &s, bool adjoint, D1 *out)
 {
-    // calls > 1 (shared control only): B = calls x Bcall rows, one batch group per call
-    if (calls > 1 && (control != PHX_CTRL_SHARED || B % calls != 0)) return false;
-    const int Bcall = calls > 1 ? B / calls : 0;
-    const int cus = cus_given > 0 ? cus_given : num_cus();
-    if (cus <= 0 || force_v0()) return false;
-    // H > 128: the hidden layer is cut into HC chunks of Hc <= 128 rows whose weights take turns in LDS
-    const int HC = (H + 127) / 128, Hc = (H + HC - 1) / HC;
+    if (s.cus <= 0 || (adjoint && s.calls > 1)) return false;
+    const Switches sw = read_switches(SW_MAXNW);
+    if (sw.v0) return false;
+    const int HC = (s.H + 127) / 128, Hc = (s.H + HC - 1) / HC;
     const int HT = solve_ht(HC, Hc);
-    if (HC > 1) nvec += (nvec >= NVEC_ADJ) ? (NVEC_ADJ_CH - NVEC_ADJ) : (NVEC_FWD_CH - NVEC_FWD);
-    const size_t blkbytes = (size_t)blk_floats_ch(HT, Hc) * 4 + lds_per_block_extra;
-    const int nblk = (N + 31) / 32, ntt = ((Bcall ? Bcall : B) + 15) / 16;
-    long long best_cost = -1;
-    D1 best{};
-    int nwmax = std::min(nw_cap, (HT == 3 ? 8 : 4));
-    if (const char *e = getenv("PHX_V1_MAXNW")) nwmax = std::min(nwmax, std::max(1, atoi(e)));
-    for (int NW = nwmax; NW >= 1; NW >>= 1)
-        for (int TPW = 1; TPW <= 4; TPW <<= 1) {
-            const int slots = NW * TPW, TG = Bcall ? calls : (ntt + slots - 1) / slots;
-            if (Bcall && slots < ntt) continue;   // a call is one group
-            // a single group smaller than its wave slots: the spare waves become helpers of the exchange (the
-            // reduce-scatter splits a row's members over all NW waves), the tile count is what the batch needs
-            const int ntg = (TG == 1 || Bcall) ? std::min(slots, ntt) : slots, Bt = 16 * ntg;
-            const bool helpers = ntg < slots;
-            if (control == PHX_CTRL_SHARED && TG != 1 && !Bcall) continue;
-            const size_t cb = ctl_bytes(Bt) + ctl_extra_per_traj * Bt;
-            if (cb + blkbytes > LDS_BUDGET) continue;
-            const int NBmax = (int)std::min<size_t>((LDS_BUDGET - cb) / blkbytes, 8);
-            for (int NB = 1; NB <= NBmax; ++NB) {
-                const int G = (nblk + NB - 1) / NB;
-                if ((long long)TG * G > cus) continue;
-                // per-SIMD MFMA work ~ TPW*NB*ceil(NW/4); prefer 2 waves per SIMD (latency hiding)
-                // tie-break: fewer trajectories per group = smaller exchange volume and fewer members per reduction
-                // (the forward kernel is lighter on registers and measured faster with two waves per SIMD)
-                const long long cost = (long long)TPW * NB * ((NW + 3) / 4) * 1000 + (nw_cap >= 8 ? (8 - NW) * 100 : 0) + Bt / 4 -
-                                       (helpers && TPW == 1 ? 50 : 0);
-                if (best_cost < 0 || cost < best_cost) {
-                    best_cost = cost;
-                    best.N = N; best.H = H; best.B = B; best.T = T; best.HT = HT; best.NB = NB; best.NW = NW;
-                    best.TPW = TPW; best.G = G; best.TG = TG; best.nblk = nblk; best.ntg = ntg; best.Bt = Bt;
-                    best.nvec = nvec; best.BN = (long long)B * N; best.HC = HC; best.Hc = Hc;
-                    best.Bcall = Bcall; best.cntN = (long long)(Bcall ? Bcall : B) * N;
-                }
-                break;  // smallest feasible NB for this (NW, TPW) is the cheapest
-            }
-        }
-    (void)fwidth;
-    if (best_cost < 0) return false;
-    *out = best;
-    return true;
+    const int nvec = adjoint ? (HC > 1 ? NVEC_ADJ_CH : NVEC_ADJ) : (HC > 1 ? NVEC_FWD_CH : NVEC_FWD);
+    const int nw_cap = adjoint ? 4 : 8;
+    const size_t ctl_per_traj = adjoint ? 40 : 0;
+    return plan_resident(s, make_tiles(HT, HC, Hc, nvec), std::min({nw_cap, HT == 3 ? 8 : 4, sw.v1_maxnw}), adjoint ? 0 : 8, 1,
+                         [&](int, int, int, int, int Bt) { return ctl_bytes(Bt) + ctl_per_traj * Bt; }, out);
 }
-
-
-// `calls` independent shared-control odeint calls of B/calls rows each: the largest number of calls one launch takes
-// (one batch group per call), 0 when not even a single call can be planned.
-int pick_calls_v1(int N, int H, int B, int T, int calls)
-{
-    if (calls < 1 || B % calls != 0) return 0;
-    const int Bcall = B / calls;
-    D1 d1;
-    for (int n = std::min(calls, std::max(1, num_cus())); n >= 1; --n)
-        if (plan_v1(N, H, n * Bcall, T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, &d1, 0, 8, n)) return n;
-    return 0;
-}
-
-// ... where every call has a time grid of its own (phx_solve_opts.t_per_sample under shared control): the first of
-// k1_solve_fwd3, k1_solve_fwd3c (dopri5) and k1_solve_fwd that plans a call, and the largest number of calls one launch of
-// it takes (every workgroup resident: TG * G <= cus).  cus <= 0: sized for 256 CUs (no device in sight).
-const Backend &v1_fwd_backend();
-struct CallsPick {
-    const Backend *be;   // null: no kernel plans a call of this shape
-    int n;               // calls per launch
-    int cus;
-};
-bool plan_calls(const CallsPick &k, int N, int H, int Bcall, int n, int T, D1 *d)
-{
-    if (k.be == &fwd3_backend()) return plan_fwd3_calls(k.cus, N, H, Bcall, n, T, d);
-    if (k.be == &fwd3c_backend()) return plan_fwd3c_calls(k.cus, N, H, Bcall, n, T, d);
-    return plan_v1(N, H, n * Bcall, T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, d, 0, 8, n, k.cus);
-}
-CallsPick pick_calls_grids(int cus, int N, int H, int Bcall, int calls, int T, int method)
-{
-    if (cus <= 0) cus = 256;
-    if (N <= 0 || H <= 0 || Bcall <= 0 || calls < 1 || method < PHX_EULER || method > PHX_DOPRI5) return {nullptr, 0, cus};
-    const Backend *const list[] = {&fwd3_backend(), &fwd3c_backend(), &v1_fwd_backend()};
-    for (const Backend *be : list) {
-        if (be->id != 1 && method != PHX_DOPRI5) continue;
-        const CallsPick k{be, 0, cus};
-        D1 d;
-        if (!plan_calls(k, N, H, Bcall, 1, T, &d)) continue;
-        for (int n = std::min(calls, cus); n > 1; --n)
-            if (plan_calls(k, N, H, Bcall, n, T, &d)) return {be, n, cus};
-        return {be, 1, cus};
-    }
-    return {nullptr, 0, cus};
-}
-
-bool plan_v1_fwd(int N, int H, int B, int T, int control, int /* method: any */, D1 *out)
-{
-    return plan_v1(N, H, B, T, control, NVEC_FWD, 2, 0, out);
-}
-bool plan_v1_adj(int N, int H, int B, int T, int control, int /* method: any */, D1 *out)
-{
-    return plan_v1(N, H, B, T, control, NVEC_ADJ, 4, ADJ_LDS_EXTRA, out, 40, ADJ_NW_CAP);
-}
+bool plan_v1_fwd(const Shape &s, D1 *out) { return plan_v1(s, false, out); }
+bool plan_v1_adj(const Shape &s, D1 *out) { return plan_v1(s, true, out); }
 
 // ftiles: hidden fragment tiles exchanged per trajectory tile (2HT forward, 4HT adjoint)
 Regions make_layout1(const D1 &d, int ftiles, bool grads, int zslots)
 {
-    Regions L{};
-    Take take;
-    const size_t R = (size_t)d.ntg * ftiles * d.HC * 4 + d.ntg;   // hidden rows (all chunks) + norm rows per group
-    L.cnt = take(4096);
-    L.part = take((size_t)d.TG * d.G * R * 64 * 8);
-    L.zbuf = take((size_t)zslots * d.TG * R * 64 * 8);
-    L.xbytes = take.off - L.part;                           // granule buffers are zeroed before every launch
-    L.scratch = take((size_t)d.TG * d.G * d.nvec * d.ntg * d.NB * 512 * 4);
-    L.pp = (long long)align_up((size_t)4 * d.H * d.N + d.N + 2 * d.H, 4);
+    LayoutSpec s;
+    s.part_rows = s.zbuf_rows = (size_t)d.ntg * ftiles * d.HC * 4 + d.ntg;   // hidden rows (all chunks) + norm rows per group
+    s.zslots = zslots;
+    s.tail = true;
+    s.pp = (long long)align_up((size_t)4 * d.H * d.N + d.N + 2 * d.H, 4);
     // partials of waves that own tiles (helper waves of a single small group write none); the quadrature pass
     // first-touches every element of them (plain stores) when T >= 2
-    L.nparts = d.TG == 1 ? (d.ntg + d.TPW - 1) / d.TPW : d.TG * d.NW;
-    L.dtheta = take(grads ? (size_t)L.pp * 4 * d.TG * d.NW : 0);
-    L.prof = take((size_t)d.TG * d.G * 16 * 8);
-    L.wimg = take((size_t)d.nblk * d.HC * blk_floats_ch(d.HT, d.Hc) * 4);
-    L.total = take.off;
-    return L;
+    s.nparts = d.TG == 1 ? (d.ntg + d.TPW - 1) / d.TPW : d.TG * d.NW;
+    s.dtheta = grads ? (size_t)s.pp * 4 * d.TG * d.NW : 0;
+    return make_regions(d, s);
 }
 Regions layout_v1_fwd(const D1 &d, bool) { return make_layout1(d, 2 * d.HT, false, 1); }
 Regions layout_v1_adj(const D1 &d, bool) { return make_layout1(d, 4 * d.HT, true, 7); }   // (partials also without gradients)
 
-void pack_v1(SolveArgs &a, const phx_params *p, hipStream_t st)
-{
-    const D1 &d = a.d;
-    if (p->wimg) a.w.wimg = (const float *)p->wimg;   // packed once by the caller for these parameter values
-    else
-        hipLaunchKernelGGL(k1_pack_images, dim3(d.nblk * d.HC), dim3(256), 0, st, to_net(p), (float *)a.w.wimg, d.HT, d.HC,
-                           d.Hc, blk_floats_ch(d.HT, d.Hc));
-}
+size_t lds_v1_fwd(const D1 &d) { return (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + ctl_bytes(d.Bt); }
+size_t lds_v1_adj(const D1 &d) { return lds_v1_fwd(d) + (size_t)40 * d.Bt; }
 
 const void *prepare_v1_fwd(SolveArgs &a, const phx_params *p, hipStream_t st)
 {
     const D1 &d = a.d;
-    pack_v1(a, p, st);
-    a.lds = (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + ctl_bytes(d.Bt);
+    pack_images(a, p, st);
     if (d.HC > 1)
         return d.HT == 7 ? reinterpret_cast<const void *>(k1_solve_fwd<7, 256, true>)
                          : reinterpret_cast<const void *>(k1_solve_fwd<8, 256, true>);
@@ -971,12 +871,11 @@ const void *prepare_v1_fwd(SolveArgs &a, const phx_params *p, hipStream_t st)
 const void *prepare_v1_adj(SolveArgs &a, const phx_params *p, hipStream_t st)
 {
     const D1 &d = a.d;
-    pack_v1(a, p, st);
-    a.lds = (size_t)blk_floats_ch(d.HT, d.Hc) * 4 * d.NB + ADJ_LDS_EXTRA * d.NB + ctl_bytes(d.Bt) + (size_t)40 * d.Bt;
+    pack_images(a, p, st);
     if (d.HC > 1)
         return d.HT == 7 ? reinterpret_cast<const void *>(k1_solve_adj<7, 256, true>)
                          : reinterpret_cast<const void *>(k1_solve_adj<8, 256, true>);
-    // (HT = 3: NW <= ADJ_NW_CAP = 4, the kernel's LDS combine layout relies on it)
+    // (HT = 3: NW <= 4, the kernel's LDS combine layout relies on it: plan_v1)
     return d.HT == 3 ? reinterpret_cast<const void *>(k1_solve_adj<3, 256, false>)
                      : reinterpret_cast<const void *>(k1_solve_adj<8, 256, false>);
 }
@@ -1000,14 +899,14 @@ bool reduce_v1(const SolveArgs &a, int npart, const phx_grads *g, int overwrite,
 
 const Backend &v1_fwd_backend()
 {
-    static const Backend b = {1, false, false, false,
-                                    plan_v1_fwd, layout_v1_fwd, plan6_ht, prepare_v1_fwd, launch_v1_fwd, nullptr, true};
+    static const Backend b = {1, false, false, false, plan_v1_fwd, layout_v1_fwd, lds_v1_fwd, plan6_ht, prepare_v1_fwd,
+                              launch_v1_fwd, nullptr, true};
     return b;
 }
 const Backend &v1_adj_backend()
 {
-    static const Backend b = {1, false, false, false,
-                                    plan_v1_adj, layout_v1_adj, plan6_ht, prepare_v1_adj, launch_v1_adj, reduce_v1, true};
+    static const Backend b = {1, false, false, false, plan_v1_adj, layout_v1_adj, lds_v1_adj, plan6_ht, prepare_v1_adj,
+                              launch_v1_adj, reduce_v1, true};
     return b;
 }
 
@@ -1022,16 +921,49 @@ const Backend *const *backends(int op)
     return op == PHX_OP_ODEINT ? fwd : op == PHX_OP_ADJOINT ? adj : none;
 }
 
+// where no device is in sight a size query plans for the 256 CUs of an MI355X
+inline int cus_or_mi355x(int cus) { return cus > 0 ? cus : 256; }
+
 // Trajectories per launch: B when one launch takes the batch; else, under per-trajectory control (trajectories are
 // independent), the largest power of two <= 4096 that the plan accepts; 0: no plan.
-int pick_chunk(const Backend &be, int N, int H, int B, int T, int control, int method)
+int pick_chunk(const Backend &be, int cus, int N, int H, int B, int T, int control, int method)
 {
     D1 d;
-    if (be.plan(N, H, B, T, control, method, &d)) return B;
+    if (be.plan({cus, N, H, B, T, control, method, 1}, &d)) return B;
     if (control != PHX_CTRL_PER_TRAJECTORY) return 0;
     for (int bc = 4096; bc >= 16; bc >>= 1)
-        if (bc < B && be.plan(N, H, bc, T, control, method, &d)) return bc;
+        if (bc < B && be.plan({cus, N, H, bc, T, control, method, 1}, &d)) return bc;
     return 0;
+}
+
+// the plan of a launch of bc rows; Bcall > 0: the rows are bc / Bcall calls of Bcall rows each
+bool plan_rows(const Backend &be, int cus, int N, int H, int bc, int T, int control, int method, int Bcall, D1 *d)
+{
+    return be.plan({cus, N, H, bc, T, control, method, Bcall > 0 ? bc / Bcall : 1}, d);
+}
+
+// workspace of a batch of B rows that runs in launches of `chunk`: the largest layout among the launches of the chunk
+// size and the remainder launch (a smaller batch can plan more groups or twice the gene tiles: a larger layout)
+size_t launches_bytes(const Backend &be, int cus, int N, int H, int B, int chunk, int T, int control, int method, bool grads,
+                      int Bcall = 0)
+{
+    size_t need = 0;
+    for (const int bc : {chunk, chunk > 0 ? B % chunk : 0}) {
+        D1 d;
+        if (bc > 0 && plan_rows(be, cus, N, H, bc, T, control, method, Bcall, &d)) need = std::max(need, be.layout(d, grads).total);
+    }
+    return need;
+}
+
+// k1_solve_bp: rows per launch of a batch (a fixed grid has no controller: planned per trajectory, any batch goes in
+// chunks), and the workspace in front of the checkpoint region
+int bp_chunk(int cus, int N, int H, int B, int T, int method)
+{
+    return pick_chunk(bp_backend(), cus, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method);
+}
+size_t bp_base_bytes(int cus, int N, int H, int B, int chunk, int T, int method)
+{
+    return launches_bytes(bp_backend(), cus, N, H, B, chunk, T, PHX_CTRL_PER_TRAJECTORY, method, true);
 }
 
 struct Pick {
@@ -1041,14 +973,32 @@ struct Pick {
 
 // the first kernel of the direction that plans the batch; whole: only a plan of the whole batch in one launch counts
 // stepped: only a kernel whose fixed-grid arm takes the sub-steps of options["step_size"] counts
-Pick first_backend(int op, int N, int H, int B, int T, int control, int method, bool whole = false, bool stepped = false)
+Pick first_backend(int op, int cus, int N, int H, int B, int T, int control, int method, bool whole = false,
+                   bool stepped = false)
 {
     for (const Backend *const *b = backends(op); *b; ++b) {
         D1 d;
         if (stepped && !(*b)->substeps) continue;
-        const int chunk = !whole ? pick_chunk(**b, N, H, B, T, control, method)
-                                 : (*b)->plan(N, H, B, T, control, method, &d) ? B : 0;
+        const int chunk = !whole ? pick_chunk(**b, cus, N, H, B, T, control, method)
+                                 : (*b)->plan({cus, N, H, B, T, control, method, 1}, &d) ? B : 0;
         if (chunk > 0) return {*b, chunk};
+    }
+    return {nullptr, 0};
+}
+
+// `calls` independent shared-control odeint calls of Bcall rows each in launches of one batch group per call: the first
+// forward kernel that plans a call, and the largest number of calls one launch of it takes (every workgroup resident:
+// TG * G <= cus).  grids: every call has a time grid of its own (phx_solve_opts.t_per_sample), which k1_solve_fwd3 and
+// k1_solve_fwd3c take too; else k1_solve_fwd only.
+Pick pick_calls(bool grids, int cus, int N, int H, int Bcall, int calls, int T, int method)
+{
+    if (cus <= 0 || N <= 0 || H <= 0 || Bcall <= 0 || calls < 1 || method < PHX_EULER || method > PHX_DOPRI5) return {nullptr, 0};
+    for (const Backend *const *b = backends(PHX_OP_ODEINT); *b; ++b) {
+        D1 d;
+        if ((!grids && (*b)->id != 1) || !plan_rows(**b, cus, N, H, Bcall, T, PHX_CTRL_SHARED, method, Bcall, &d)) continue;
+        for (int n = std::min(calls, cus); n > 1; --n)
+            if (plan_rows(**b, cus, N, H, n * Bcall, T, PHX_CTRL_SHARED, method, Bcall, &d)) return {*b, n * Bcall};
+        return {*b, Bcall};
     }
     return {nullptr, 0};
 }
@@ -1080,7 +1030,9 @@ struct SolveCall {
     double step = 0.0;   // SolveCfg::step
     int control = -1;    // >= 0: the step control the launches are planned and run with instead of o->control
     float *ckpt = nullptr;   // k1_solve_bp: the checkpoint region behind the launches' layouts
-    int Bcall = 0;       // > 0 with o->t_per_sample: t is [calls, T], one row per call of Bcall trajectories
+    int K = 0;           // ... and the grid steps per trajectory it holds (D1::K)
+    int Bcall = 0;       // > 0: the batch is calls of Bcall trajectories, a launch takes whole calls (D1::Bcall); with
+                         // o->t_per_sample t is [calls, T], one row per call
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1097,11 +1049,12 @@ struct EventPair {
     ~EventPair() { end(); }
 };
 
-// Runs a batch on kernel family `be` in launches of `chunk` trajectories: pointers are offset to a launch's rows, the
-// [T,B,N] time stride stays B*N, later launches add their parameter gradients.  plan(bc, &d): the plan of a launch of bc.
-template <typename Plan>
-int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
+// Runs a batch on kernel family k.be in launches of k.chunk trajectories, each planned for `cus` CUs: pointers are offset
+// to a launch's rows, the [T,B,N] time stride stays B*N, later launches add their parameter gradients.
+int run_solve(const Pick &k, int cus, const SolveCall &c)
 {
+    const Backend &be = *k.be;
+    const int chunk = k.chunk, control = c.control >= 0 ? c.control : c.o->control;
     const phx_params *p = c.p;
     const phx_solve_opts *o = c.o;
     SolveArgs a{};
@@ -1116,7 +1069,8 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
     EventPair ev{c.st};
     for (int b0 = 0; b0 < c.B; b0 += chunk) {
         D1 &d = a.d;
-        if (!plan(std::min(chunk, c.B - b0), &d)) return PHX_ERR_BAD_ARG;
+        if (!plan_rows(be, cus, p->N, p->H, std::min(chunk, c.B - b0), c.T, control, o->method, c.Bcall, &d)) return PHX_ERR_BAD_ARG;
+        d.K = c.K;
         d.BN = (long long)c.B * p->N;   // time stride of the caller's [T,B,N] arrays
         const long long r0 = (long long)b0 * p->N;
         auto rows = [&](auto *q) { return q ? q + r0 : q; };
@@ -1152,6 +1106,7 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
         if (c.grads && (be.zero_dtheta_always || c.T < 2) &&
             hipMemsetAsync(w.dtheta, 0, sizeof(float) * (size_t)L.pp * L.nparts, c.st) != hipSuccess)
             return PHX_ERR_LAUNCH;
+        a.lds = be.lds(d);
         const void *fn = be.prepare(a, p, c.st);
         if (!fn) return PHX_ERR_BAD_ARG;
         // the workgroups of a launch wait for each other's rows: refuse a grid the device cannot hold at once
@@ -1164,14 +1119,6 @@ int run_solve(const Backend &be, int chunk, Plan plan, const SolveCall &c)
             return PHX_ERR_LAUNCH;
     }
     return PHX_OK;
-}
-
-int run_solve(const Pick &k, const SolveCall &c)
-{
-    const Backend &be = *k.be;
-    const int control = c.control >= 0 ? c.control : c.o->control;
-    return run_solve(be, k.chunk, [&](int bc, D1 *d) { return be.plan(c.p->N, c.p->H, bc, c.T, control, c.o->method, d); },
-                     c);
 }
 
 
@@ -1614,13 +1561,33 @@ void phx_debug_set_kernel_events(void *ev_start, void *ev_stop)
 int phx_debug_profile_region(int op, int N, int H, int B, int T, int control, size_t *offset, int *n_workgroups,
                              int *plan /* [NW, TPW, NB, G, TG, HT] */)
 {
-    const Pick k = first_backend(op, N, H, B, T, control, PHX_DOPRI5, true);   // (the plan of a one-launch batch)
+    const int cus = num_cus();
+    const Pick k = first_backend(op, cus, N, H, B, T, control, PHX_DOPRI5, true);   // (the plan of a one-launch batch)
     D1 d1;
-    if (!k.be || !k.be->plan(N, H, B, T, control, PHX_DOPRI5, &d1)) return PHX_ERR_BAD_ARG;
+    if (!k.be || !k.be->plan({cus, N, H, B, T, control, PHX_DOPRI5, 1}, &d1)) return PHX_ERR_BAD_ARG;
     *offset = k.be->layout(d1, true).prof;
     *n_workgroups = d1.TG * d1.G;
     if (plan) { plan[0] = d1.NW; plan[1] = d1.TPW; plan[2] = d1.NB; plan[3] = d1.G; plan[4] = d1.TG; plan[5] = k.be->plan6(d1); }
     return PHX_OK;
+}
+
+int phx_debug_plan(int op, int kernel_id, int cus, int N, int H, int B, int T, int control, int method, int calls,
+                   long long *out)
+{
+    const Backend *be = op == PHX_OP_ADJOINT && kernel_id == bp_backend().id ? &bp_backend() : nullptr;
+    for (const Backend *const *b = backends(op); *b && !be; ++b)
+        if ((*b)->id == kernel_id) be = *b;
+    D1 d;
+    if (!be || !out || calls < 1 || !be->plan({cus, N, H, B, T, control, method, calls}, &d)) return 0;
+    const Regions L = be->layout(d, true);
+    const long long v[PHX_DEBUG_PLAN_FIELDS] = {
+        d.N, d.H, d.B, d.T, d.HT, d.NB, d.NW, d.TPW, d.G, d.TG, d.nblk, d.ntg, d.Bt, d.nvec, d.BN, d.HC, d.Hc, d.Bcall, d.cntN,
+        d.res, d.hb, d.split,
+        (long long)L.total, (long long)L.cnt, (long long)L.part, (long long)L.zbuf, (long long)L.part1, (long long)L.zbuf1,
+        (long long)L.scratch, (long long)L.dtheta, (long long)L.prof, (long long)L.wimg, (long long)L.hq, (long long)L.xbytes,
+        L.pp, L.nparts, (long long)be->lds(d)};
+    std::copy(v, v + PHX_DEBUG_PLAN_FIELDS, out);
+    return PHX_DEBUG_PLAN_FIELDS;
 }
 
 int phx_debug_adjoint_kernel(int N, int H, int B, int T, int control)
@@ -1632,27 +1599,27 @@ int phx_debug_adjoint_kernel_m(int N, int H, int B, int T, int control, int meth
 {
     if (method & 0x100)   // the kernel of a solve with a step size (planned per trajectory); 0: none, the solve is refused
         return [&] {
-            const Pick s = first_backend(PHX_OP_ADJOINT, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
+            const Pick s = first_backend(PHX_OP_ADJOINT, num_cus(), N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
             return s.be ? s.be->id : 0;
         }();
-    const Pick k = first_backend(PHX_OP_ADJOINT, N, H, B, T, control, method);
+    const Pick k = first_backend(PHX_OP_ADJOINT, num_cus(), N, H, B, T, control, method);
     return k.be ? k.be->id : 0;
 }
 
 int phx_debug_forward_kernel_m(int N, int H, int B, int T, int control, int method)
 {
     if (method & 0x100) {   // as in phx_debug_adjoint_kernel_m
-        const Pick s = first_backend(PHX_OP_ODEINT, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
+        const Pick s = first_backend(PHX_OP_ODEINT, num_cus(), N, H, B, T, PHX_CTRL_PER_TRAJECTORY, method & 0xff, false, true);
         return s.be ? s.be->id : 0;
     }
-    const Pick k = first_backend(PHX_OP_ODEINT, N, H, B, T, control, method);
+    const Pick k = first_backend(PHX_OP_ODEINT, num_cus(), N, H, B, T, control, method);
     return k.be ? k.be->id : 0;
 }
 
 int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, int method)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 0 || (op != PHX_OP_ODEINT && op != PHX_OP_ADJOINT)) return 0;
-    const Pick k = first_backend(op, N, H, B, T, control, method);
+    const Pick k = first_backend(op, num_cus(), N, H, B, T, control, method);
     if (!k.be) return 1;   // the VALU engine takes any batch in one launch
     return (B + k.chunk - 1) / k.chunk;
 }
@@ -1660,13 +1627,13 @@ int phx_debug_solve_launches(int op, int N, int H, int B, int T, int control, in
 int phx_debug_backprop_kernel_m(int N, int H, int B, int T, int method)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 1 || method < PHX_EULER || method > PHX_RK4) return 0;
-    return bp_chunk(num_cus(), N, H, B, T) > 0 ? bp_backend().id : 0;
+    return bp_chunk(cus_or_mi355x(num_cus()), N, H, B, T, method) > 0 ? bp_backend().id : 0;
 }
 
 int phx_debug_backprop_launches(int N, int H, int B, int T, int method)
 {
     if (phx_debug_backprop_kernel_m(N, H, B, T, method) == 0) return 0;
-    const int chunk = bp_chunk(num_cus(), N, H, B, T);
+    const int chunk = bp_chunk(cus_or_mi355x(num_cus()), N, H, B, T, method);
     return (B + chunk - 1) / chunk;
 }
 
@@ -1677,9 +1644,9 @@ int phx_debug_backprop_plan(int cus, int N, int H, int B, int T, int method, int
     if (N <= 0 || H <= 0 || B <= 0 || T < 1 || method < PHX_EULER || method > PHX_RK4) return 0;
     if (cus <= 0) cus = num_cus();
     if (cus <= 0) return 0;                        // no device to ask
-    const int chunk = bp_chunk(cus, N, H, B, T);
+    const int chunk = bp_chunk(cus, N, H, B, T, method);
     D1 d;
-    if (chunk <= 0 || !bp_plan(cus, N, H, std::min(chunk, B), T, &d)) return 0;
+    if (chunk <= 0 || !bp_backend().plan({cus, N, H, std::min(chunk, B), T, PHX_CTRL_PER_TRAJECTORY, method, 1}, &d)) return 0;
     if (plan) {
         const int v[8] = {d.HT, d.NB, d.G, d.TG, d.ntg, d.nblk, chunk, (B + chunk - 1) / chunk};
         for (int i = 0; i < 8; ++i) plan[i] = v[i];
@@ -1690,10 +1657,10 @@ int phx_debug_backprop_plan(int cus, int N, int H, int B, int T, int method, int
 size_t phx_odeint_backprop_workspace_bytes(int N, int H, int B, int T, long long grid_steps)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 1 || grid_steps < 0) return 0;
-    const int cus = num_cus();
-    const int chunk = bp_chunk(cus, N, H, B, T);
+    const int cus = cus_or_mi355x(num_cus());
+    const int chunk = bp_chunk(cus, N, H, B, T, PHX_EULER);   // (the fixed-grid methods plan alike)
     if (chunk <= 0) return 0;
-    return bp_base_bytes(cus, N, H, B, T) + align_up((size_t)grid_steps * chunk * N * 4, 256);
+    return bp_base_bytes(cus, N, H, B, chunk, T, PHX_EULER) + align_up((size_t)grid_steps * chunk * N * 4, 256);
 }
 
 size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
@@ -1701,16 +1668,12 @@ size_t phx_workspace_bytes(int op, int N, int H, int B, int T)
     if (N <= 0 || H <= 0 || B <= 0 || T < 0) return 0;
     const Dims d = make_dims(N, H, B, T, PHX_CTRL_PER_TRAJECTORY);
     size_t need = make_layout(d, op).total;
-    // every persistent kernel of a solve direction under both control modes: the launches of the chunk size and the
-    // remainder launch (a smaller batch can plan more groups or twice the gene tiles: a larger layout)
+    // every persistent kernel of a solve direction under both control modes
+    const int cus = num_cus();
     for (const Backend *const *b = backends(op); *b; ++b)
-        for (int ctl = 0; ctl < 2; ++ctl) {
-            const int chunk = pick_chunk(**b, N, H, B, T, ctl, PHX_DOPRI5);
-            for (const int bc : {chunk, chunk > 0 ? B % chunk : 0}) {
-                D1 d1;
-                if (bc > 0 && (*b)->plan(N, H, bc, T, ctl, PHX_DOPRI5, &d1)) need = std::max(need, (*b)->layout(d1, true).total);
-            }
-        }
+        for (int ctl = 0; ctl < 2; ++ctl)
+            need = std::max(need, launches_bytes(**b, cus, N, H, B, pick_chunk(**b, cus, N, H, B, T, ctl, PHX_DOPRI5), T, ctl,
+                                                 PHX_DOPRI5, true));
     if (op == PHX_OP_RHS_FORWARD) {
         PlanBatch pb;
         if (plan_batch(N, H, B, &pb)) need = std::max(need, pb.total_fwd);   // (whether the chain runs depends on the call's images)
@@ -1758,10 +1721,11 @@ size_t phx_odeint_calls_workspace_bytes(int N, int H, int B, int T, int calls)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return 0;
     if (calls == 1) return phx_workspace_bytes(PHX_OP_ODEINT, N, H, B, T);
-    const int n = pick_calls_v1(N, H, B, T, calls);
+    const int cus = num_cus(), Bc = B / calls;
+    const Pick k = pick_calls(false, cus, N, H, Bc, calls, T, PHX_DOPRI5);   // (k1_solve_fwd plans every method alike)
     D1 d1;
-    if (n < 1 || !plan_v1(N, H, n * (B / calls), T, PHX_CTRL_SHARED, NVEC_FWD, 2, 0, &d1, 0, 8, n)) return 0;
-    return layout_v1_fwd(d1, false).total;
+    if (!k.be || !plan_rows(*k.be, cus, N, H, k.chunk, T, PHX_CTRL_SHARED, PHX_DOPRI5, Bc, &d1)) return 0;
+    return k.be->layout(d1, false).total;
 }
 
 int phx_debug_calls_grids_plan(int N, int H, int B, int T, int calls, int method, int *plan)
@@ -1769,13 +1733,14 @@ int phx_debug_calls_grids_plan(int N, int H, int B, int T, int calls, int method
     if (plan)
         for (int i = 0; i < 6; ++i) plan[i] = 0;
     if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return 0;
-    const CallsPick k = pick_calls_grids(num_cus(), N, H, B / calls, calls, T, method);
+    const int cus = cus_or_mi355x(num_cus()), Bc = B / calls;
+    const Pick k = pick_calls(true, cus, N, H, Bc, calls, T, method);
     D1 d;
-    if (!k.be || !plan_calls(k, N, H, B / calls, k.n, T, &d)) return 0;
+    if (!k.be || !plan_rows(*k.be, cus, N, H, k.chunk, T, PHX_CTRL_SHARED, method, Bc, &d)) return 0;
     if (plan) {
-        plan[0] = k.be->id; plan[1] = d.TG; plan[2] = d.G; plan[3] = d.NW; plan[4] = d.ntg; plan[5] = k.cus;
+        plan[0] = k.be->id; plan[1] = d.TG; plan[2] = d.G; plan[3] = d.NW; plan[4] = d.ntg; plan[5] = cus;
     }
-    return k.n;
+    return k.chunk / Bc;
 }
 
 int phx_debug_calls_grids_kernel_m(int N, int H, int B, int T, int calls, int method)
@@ -1793,15 +1758,9 @@ int phx_debug_calls_grids_launches(int N, int H, int B, int T, int calls, int me
 size_t phx_odeint_calls_grids_workspace_bytes(int N, int H, int B, int T, int calls, int method)
 {
     if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return 0;
-    const int Bc = B / calls;
-    const CallsPick k = pick_calls_grids(num_cus(), N, H, Bc, calls, T, method);
-    if (!k.be) return 0;
-    size_t need = 0;
-    for (const int n : {k.n, calls % k.n}) {   // the launches of k.n calls and the remainder launch
-        D1 d;
-        if (n > 0 && plan_calls(k, N, H, Bc, n, T, &d)) need = std::max(need, k.be->layout(d, false).total);
-    }
-    return need;
+    const int cus = cus_or_mi355x(num_cus()), Bc = B / calls;
+    const Pick k = pick_calls(true, cus, N, H, Bc, calls, T, method);
+    return k.be ? launches_bytes(*k.be, cus, N, H, B, k.chunk, T, PHX_CTRL_SHARED, method, false, Bc) : 0;
 }
 
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,
@@ -1861,8 +1820,7 @@ int phx_rhs_vjp(const phx_params *p, const float *y, const float *cot, float *vj
                 float *f_out, int B, int prior_only, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (bad_params(p) || !y || !cot || B <= 0 || !workspace) return PHX_ERR_BAD_ARG;
-    if (grads && (!grads->Ws || !grads->bs || !grads->Wp || !grads->bp || (!grads->WaT && !grads->Wa) || !grads->g))
-        return PHX_ERR_BAD_ARG;
+    if (bad_grads(grads)) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (prior_only && grads && !vjp_y && !f_out) {   // the prior branch's backward: MFMA parameter gradients
         PlanBatch pb;
@@ -1959,6 +1917,7 @@ int phx_odeint_stepped(const phx_params *p, const float *y0_all, const double *t
     // a shared controller has one time grid -- unless the batch is several calls: then one row of t per call
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample && o->calls <= 1) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
+    const int cus = num_cus();
     SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
                 workspace, workspace_bytes, st};
     if (is_stepped(o, step_size)) {
@@ -1968,30 +1927,21 @@ int phx_odeint_stepped(const phx_params *p, const float *y0_all, const double *t
         if (o->calls > 1) return PHX_ERR_BAD_ARG;
         c.step = step_size;
         c.control = PHX_CTRL_PER_TRAJECTORY;
-        const Pick k = first_backend(PHX_OP_ODEINT, p->N, p->H, B, T, c.control, o->method, false, true);
-        return k.be ? run_solve(k, c) : (int)PHX_ERR_BAD_ARG;
+        const Pick k = first_backend(PHX_OP_ODEINT, cus, p->N, p->H, B, T, c.control, o->method, false, true);
+        return k.be ? run_solve(k, cus, c) : (int)PHX_ERR_BAD_ARG;
     }
     // several calls in one batch (analysis callers): every call keeps its own shared controller, a launch takes as many
-    // calls as there are batch groups to run them (first-generation kernel only)
+    // calls as there are batch groups to run them: the first-generation kernel, or with a time grid per call
+    // (t_per_sample) the dopri5 kernels of the third generation too, where they plan the call
     if (o->calls > 1) {
         if (o->control != PHX_CTRL_SHARED || B % o->calls != 0) return PHX_ERR_BAD_ARG;
-        if (o->t_per_sample) {   // a time grid per call: the dopri5 kernels of the third generation where they plan the call
-            const int cus = num_cus();
-            if (cus <= 0) return PHX_ERR_LAUNCH;
-            const int Bc = B / o->calls;
-            const CallsPick k = pick_calls_grids(cus, p->N, p->H, Bc, o->calls, T, o->method);
-            if (!k.be) return PHX_ERR_BAD_ARG;
-            c.Bcall = Bc;
-            return run_solve(*k.be, k.n * Bc, [&](int bc, D1 *d) { return plan_calls(k, p->N, p->H, Bc, bc / Bc, T, d); }, c);
-        }
-        const int Bcall = B / o->calls, chunk = pick_calls_v1(p->N, p->H, B, T, o->calls) * Bcall;
-        if (chunk == 0) return PHX_ERR_BAD_ARG;
-        return run_solve(v1_fwd_backend(), chunk, [&](int bc, D1 *d) {
-            return plan_v1(p->N, p->H, bc, T, o->control, NVEC_FWD, 2, 0, d, 0, 8, bc / Bcall);
-        }, c);
+        if (o->t_per_sample && cus <= 0) return PHX_ERR_LAUNCH;
+        c.Bcall = B / o->calls;
+        const Pick k = pick_calls(o->t_per_sample != 0, cus, p->N, p->H, c.Bcall, o->calls, T, o->method);
+        return k.be ? run_solve(k, cus, c) : (int)PHX_ERR_BAD_ARG;
     }
-    const Pick k = first_backend(PHX_OP_ODEINT, p->N, p->H, B, T, o->control, o->method);
-    if (k.be) return run_solve(k, c);
+    const Pick k = first_backend(PHX_OP_ODEINT, cus, p->N, p->H, B, T, o->control, o->method);
+    if (k.be) return run_solve(k, cus, c);
     const Dims d = make_dims(p->N, p->H, B, T, o->control);
     const Layout L = make_layout(d, PHX_OP_ODEINT);
     if (workspace_bytes < L.total) return PHX_ERR_WORKSPACE;
@@ -2024,22 +1974,22 @@ int phx_odeint_adjoint_backward_stepped(const phx_params *p, const double *t_all
     if (bad_params(p) || !t_all || !o || !y_saved_all || !grad_y_all || !adj_y0_all || !status_all || !nfe_all ||
         !nsteps_all || B <= 0 || T < 1 || !workspace)
         return PHX_ERR_BAD_ARG;
-    if (grads && (!grads->Ws || !grads->bs || !grads->Wp || !grads->bp || (!grads->WaT && !grads->Wa) || !grads->g))
-        return PHX_ERR_BAD_ARG;
+    if (bad_grads(grads)) return PHX_ERR_BAD_ARG;
     if (o->method < PHX_EULER || o->method > PHX_DOPRI5) return PHX_ERR_BAD_ARG;
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
+    const int cus = num_cus();
     if (is_stepped(o, step_size)) {   // as in phx_odeint_stepped
         SolveCall c{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all, nfe_all, nsteps_all,
                     grads, workspace, workspace_bytes, st};
         c.step = step_size;
         c.control = PHX_CTRL_PER_TRAJECTORY;
-        const Pick k = first_backend(PHX_OP_ADJOINT, p->N, p->H, B, T, c.control, o->method, false, true);
-        return k.be ? run_solve(k, c) : (int)PHX_ERR_BAD_ARG;
+        const Pick k = first_backend(PHX_OP_ADJOINT, cus, p->N, p->H, B, T, c.control, o->method, false, true);
+        return k.be ? run_solve(k, cus, c) : (int)PHX_ERR_BAD_ARG;
     }
-    const Pick k = first_backend(PHX_OP_ADJOINT, p->N, p->H, B, T, o->control, o->method);
+    const Pick k = first_backend(PHX_OP_ADJOINT, cus, p->N, p->H, B, T, o->control, o->method);
     if (k.be)
-        return run_solve(k, SolveCall{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all,
+        return run_solve(k, cus, SolveCall{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all,
                                       nfe_all, nsteps_all, grads, workspace, workspace_bytes, st});
     const Dims d = make_dims(p->N, p->H, B, T, o->control);
     const Layout L = make_layout(d, PHX_OP_ADJOINT);
@@ -2067,30 +2017,25 @@ int phx_odeint_backprop_backward(const phx_params *p, const double *t_all, int B
     if (bad_params(p) || !t_all || !o || !y_saved_all || !grad_y_all || !adj_y0_all || !status_all || !nfe_all ||
         !nsteps_all || B <= 0 || T < 1 || !workspace || grid_steps < 0 || grid_steps > 2147483000LL)
         return PHX_ERR_BAD_ARG;
-    if (grads && (!grads->Ws || !grads->bs || !grads->Wp || !grads->bp || (!grads->WaT && !grads->Wa) || !grads->g))
-        return PHX_ERR_BAD_ARG;
+    if (bad_grads(grads)) return PHX_ERR_BAD_ARG;
     if (o->method < PHX_EULER || o->method > PHX_RK4) return PHX_ERR_BAD_ARG;   // dopri5: no backpropagation through its steps
     if (o->control == PHX_CTRL_SHARED && o->t_per_sample) return PHX_ERR_BAD_ARG;
     const bool stepped = is_stepped(o, step_size);
     if (stepped && grid_steps < 1) return PHX_ERR_BAD_ARG;
     const int cus = num_cus();
     if (cus <= 0) return PHX_ERR_LAUNCH;
-    const int chunk = bp_chunk(cus, p->N, p->H, B, T);
+    const int chunk = bp_chunk(cus, p->N, p->H, B, T, o->method);
     if (chunk <= 0) return PHX_ERR_BAD_ARG;   // H > 128, or PHX_ENGINE=v0
     const int K = stepped ? (int)grid_steps : 0;
-    const size_t base = bp_base_bytes(cus, p->N, p->H, B, T);
+    const size_t base = bp_base_bytes(cus, p->N, p->H, B, chunk, T, o->method);
     if (workspace_bytes < base + align_up((size_t)K * chunk * p->N * 4, 256)) return PHX_ERR_WORKSPACE;
     SolveCall c{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all, nfe_all, nsteps_all,
                 grads, workspace, workspace_bytes, (hipStream_t)stream};
     c.step = stepped ? step_size : 0.0;
     c.control = PHX_CTRL_PER_TRAJECTORY;
     c.ckpt = K ? reinterpret_cast<float *>(static_cast<char *>(workspace) + base) : nullptr;
-    const Backend &be = bp_backend();
-    return run_solve(be, chunk, [&](int bc, D1 *d) {
-        if (!be.plan(p->N, p->H, bc, T, c.control, o->method, d)) return false;
-        d->K = K;
-        return true;
-    }, c);
+    c.K = K;
+    return run_solve(Pick{&bp_backend(), chunk}, cus, c);
 }
 
 }  // extern "C"

@@ -152,7 +152,7 @@ inline bool force_v0()
 namespace phxh {
 
 // workspace layout of one plan: byte offsets of the regions every family draws from (a region a family does not use has
-// zero bytes), in the family's own order
+// zero bytes), in the one order of make_regions (phx_plan.hpp)
 struct Regions {
     size_t total, cnt, part, zbuf, part1, zbuf1, scratch, dtheta, prof, wimg, hq;
     size_t xbytes;      // bytes from `part` on that a fill zeroes together with the header [cnt, part)
@@ -176,15 +176,23 @@ struct SolveArgs {
     float *ckpt;          // k1_solve_bp: checkpoint region [D1::K][rows of the launch][N] (null: none)
 };
 
+// what a launch is planned for: the CUs that must hold its workgroups at once, the batch of B rows with T time points,
+// step control and method, and calls > 1: B = calls x (B / calls) rows of independent shared-control dopri5 calls that
+// share the launch (forward kernels only, D1::Bcall); calls == 1: the ordinary plan
+struct Shape {
+    int cus, N, H, B, T, control, method, calls;
+};
+
 struct Backend {
-    int id;                    // kernel generation phx_debug_{forward,adjoint}_kernel_m report (1 .. 4)
+    int id;                    // kernel generation phx_debug_{forward,adjoint}_kernel_m report (1 .. 4; k1_solve_bp: 5)
     bool cleans_idle_set;      // the kernel cleans its idle exchange set: ws_keep may skip the fill of a one-launch batch
     bool zero_dtheta_always;   // gradient partials are zeroed before every launch, else only when T < 2 (nobody steps)
     bool prof_levels;          // PHX_PROF=<level >= 1> turns the timers on; else only a value that starts with '1'
-    bool (*plan)(int N, int H, int B, int T, int control, int method, D1 *out);
+    bool (*plan)(const Shape &s, D1 *out);   // a pure function of the shape and the switches (phx_plan.hpp)
     Regions (*layout)(const D1 &d, bool grads);
+    size_t (*lds)(const D1 &d);   // dynamic LDS bytes of the launch
     int (*plan6)(const D1 &d);   // last entry of phx_debug_profile_region's plan
-    // the images (packed into a.w.wimg unless the caller's serve), a.lds and the kernel; null: no kernel for this plan
+    // the images (packed into a.w.wimg unless the caller's serve) and the kernel; null: no kernel for this plan
     const void *(*prepare)(SolveArgs &a, const phx_params *p, hipStream_t st);
     hipError_t (*launch)(const void *fn, const SolveArgs &a, hipStream_t st);
     // backward: sums `npart` partials into the caller's gradients; false on a launch error
@@ -213,16 +221,8 @@ const Backend &fwd3c_backend();
 const Backend &adj2_backend();
 const Backend &adj3_backend();
 const Backend &adj3c_backend();
-// `calls` independent shared-control dopri5 calls of Bcall rows in ONE launch of k1_solve_fwd3 / k1_solve_fwd3c (D1::Bcall:
-// batch group g = call g); calls == 1: the ordinary one-group plan.  `cus`: the CU count the plan keeps TG * G within.
-bool plan_fwd3_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out);
-bool plan_fwd3c_calls(int cus, int N, int H, int Bcall, int calls, int T, D1 *out);
 // k1_solve_bp (backpropagation through the fixed-grid steps): not in the lists of the adjoint direction, it has entry
-// points of its own.  bp_chunk: rows per launch of a batch (0: no plan); bp_base_bytes: workspace in front of the
-// checkpoint region; both size for 256 CUs when cus <= 0 (no device in sight).  bp_plan: the plan of one launch of B rows.
+// points of its own
 const Backend &bp_backend();
-int bp_chunk(int cus, int N, int H, int B, int T);
-bool bp_plan(int cus, int N, int H, int B, int T, D1 *out);
-size_t bp_base_bytes(int cus, int N, int H, int B, int T);
 
 }  // namespace phxh
