@@ -128,6 +128,24 @@ size_t phx_odeint_calls_workspace_bytes(int N, int H, int B, int T, int calls);
  * than 256 rows of dopri5 beyond the first-generation kernel's 512, PHX_ENGINE=v0: solve the calls one by one).  Unlike
  * phx_odeint_calls_workspace_bytes it depends on the method, and it sizes for 256 CUs when no device is visible. */
 size_t phx_odeint_calls_grids_workspace_bytes(int N, int H, int B, int T, int calls, int method);
+/* In-silico knockouts (additive, ABI 7): phx_odeint with PHX_CTRL_SHARED, opts->calls = calls >= 1, opts->t_per_sample = 1
+ * and t as [calls, T], where call k integrates with gene clamp_gene[k] (DEVICE, [calls]) held at its initial value:
+ *     d y[:, clamp_gene[k]] / dt = 0      for the whole time course of call k.
+ * The RHS is f = relu(g) (W_alpha z - y) (odenet.py:85-91), so the clamped call IS the solve of the model whose g[gene]
+ * is 0, arithmetic included: the sweeps of k1_solve_fwd3 / k1_solve_fwd3c read relu(g) of that gene as 0, and stage
+ * slopes, error norm, initial step, FSAL, accept pass and dense output follow from it.  An entry no gene has (negative,
+ * >= N) clamps nothing; the list is not validated.  Level 0 in y0 is a knockout, a high level an over-expression.
+ * Served only where dopri5 plans the calls on k1_solve_fwd3 / k1_solve_fwd3c (the planning of
+ * phx_odeint_calls_grids_workspace_bytes); a batch of more calls than one launch holds goes through the shared chunk
+ * driver, list, time rows and y0 / sol rows offset together.
+ * PHX_ERR_BAD_ARG before any device call: null clamp_gene (or any pointer phx_odeint refuses), a method other than
+ * dopri5, control != PHX_CTRL_SHARED, t_per_sample == 0, calls < 1, B % calls, and a shape whose
+ * phx_odeint_clamped_workspace_bytes is 0 (the first-generation kernel would serve it, PHX_ENGINE=v0: solve the calls
+ * one by one with g[gene] zeroed).  The size query plans for 256 CUs when no device is visible. */
+size_t phx_odeint_clamped_workspace_bytes(int N, int H, int B, int T, int calls);
+int phx_odeint_clamped(const phx_params *p, const float *y0, const double *t, int B, int T, const phx_solve_opts *opts,
+                       const int *clamp_gene, float *sol, int *status, int *nfe, int *nsteps, void *workspace,
+                       size_t workspace_bytes, void *stream);
 
 /* Replaces ODENet.forward / prior_only_forward (odenet.py:85-98): out[B,N] = f(y[B,N]). */
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only,
@@ -317,6 +335,24 @@ int phx_hill_jacobian(const int *code, const int *off, const int *len, const flo
 size_t phx_influence_workspace_bytes(int T, int pairs, int B, int N);
 int phx_influence_scores(const float *sol, int T, int pairs, int B, int N, const int *genes_host, float *scores,
                          float *targets, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The scoring pass of a knockout screen: K clamped solves (phx_odeint_clamped) against ONE unperturbed solve.
+ * base [T, B, N] is the output block of the baseline, sol [T, K * B, N] that of K calls of B rows started from the same
+ * states with gene genes_host[k] (HOST, [K]) set to its clamped level.  With d = sol[tau, kB + b, n] - base[tau, b, n]
+ * over tau = 1 .. T-1 and b < B:
+ *     shift[k, n]     = mean of d          signed: does target n go up or down            (may be NULL)
+ *     magnitude[k, n] = mean of |d|                                                       (may be NULL)
+ *     scores[k]       = mean of magnitude[k, n] over n != genes[k]     (find_gene_influences.py:74-75, one shared baseline)
+ * sol is read once (its tau = 0 slab not at all); no pair layout, no replicated baseline.  Every sum runs in an order
+ * fixed by the shape (no atomics): two calls agree bit for bit, with or without the optional outputs.  Column genes[k] is
+ * left out of the score by index and reported in shift / magnitude as computed.  Non-finite inputs propagate.
+ * PHX_ERR_BAD_ARG before any device call: null base / sol / scores / genes_host, T < 2, K < 1 (or > 65535), B < 1, N < 2,
+ * a gene outside [0, N); PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_knockout_effects_workspace_bytes(T, K, B, N) (0 for a shape the call refuses): the sums live there. */
+size_t phx_knockout_effects_workspace_bytes(int T, int K, int B, int N);
+int phx_knockout_effects(const float *base, const float *sol, int T, int K, int B, int N, const int *genes_host,
+                         float *scores, float *shift, float *magnitude, void *workspace, size_t workspace_bytes,
+                         void *stream);
 
 /* The explainability matrices of a trained model, regulator i -> target j (the orientation of effects_mat and of the
  * gene-influence matrix), from the engine layout as it is.  With s = y - 0.5 and r = relu(g):

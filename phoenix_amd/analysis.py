@@ -108,6 +108,81 @@ def _fused_scan(odenet, dim, method, n, time_pts_to_project, device, genes, draw
     return scores.cpu().numpy(), matrix
 
 
+KnockoutEffects = collections.namedtuple("KnockoutEffects", ("genes", "scores", "shift", "magnitude"))
+
+
+def _knockout_args(N, genes, value, genes_per_launch):
+    """(genes, values) of `knockout_effects` as lists of G ints / floats, checked on the host before any launch"""
+    genes = list(range(N)) if genes is None else list(genes.tolist() if hasattr(genes, "tolist") else genes)
+    for g in genes:
+        if isinstance(g, bool) or not hasattr(g, "__index__"):
+            raise TypeError("knockout_effects: genes must be integers, got %r" % (g,))
+    genes = [int(g) for g in genes]
+    for g in genes:
+        if g < 0 or g >= N:
+            raise ValueError("knockout_effects: gene %d is not one of 0 .. %d" % (g, N - 1))
+    if not genes:
+        raise ValueError("knockout_effects: no gene to clamp")
+    values = value.tolist() if hasattr(value, "tolist") else value
+    if isinstance(values, (list, tuple)):
+        if len(values) != len(genes):
+            raise ValueError("knockout_effects: %d values for %d genes" % (len(values), len(genes)))
+        values = [float(v) for v in values]
+    else:
+        values = [float(values)] * len(genes)
+    if not hasattr(genes_per_launch, "__index__") or int(genes_per_launch) < 1:
+        raise ValueError("knockout_effects: genes_per_launch must be a positive integer")
+    return genes, values
+
+
+def knockout_effects(odenet, y0, genes=None, value=0.0, time_pts_to_project=None, method="dopri5", genes_per_launch=8,
+                     want_matrices=True):
+    """In-silico knockout / over-expression screen: what does the system do when gene g is HELD at `value` for the whole
+    time course?  (`gene_influence_scores` nudges only the initial value, which relaxes back under the gene's own dynamics.)
+    y0 [B, 1, N] or [B, N]: the states to start from (data states, or `rand - 0.5` like the scan); genes: the G genes to
+    clamp, one at a time (default: all N); value: a scalar or [G] levels, 0 a knockout, a large level an over-expression;
+    time_pts_to_project: default the scan's arange(0, 1, 0.1).
+    The unperturbed solve runs once.  Per block of `genes_per_launch` genes, call k starts from y0 with column genes[k]
+    set to value[k] and integrates with d y[:, genes[k]] / dt = 0 (`odeint_calls(clamp=...)`), and one pass of
+    phx_knockout_effects scores the block against the baseline; one output block is alive at a time.
+    Returns KnockoutEffects(genes, scores [G] float32 numpy, shift [G, N], magnitude [G, N] device tensors or None):
+    with d = clamped - baseline over the projected time points after the first and the B states, shift[i, n] is the mean
+    of d (signed: target n goes up or down), magnitude[i, n] the mean of |d|, scores[i] the mean of magnitude[i, n] over
+    n != genes[i] -- a per-gene vector like the influence scores, for `consolidate_gene_scores` and
+    `pathway_permutation_test` as it is."""
+    N = params_of(odenet)[0].shape[1]
+    genes, values = _knockout_args(N, genes, value, genes_per_launch)      # first: refused whatever else holds
+    if y0.shape[-1] != N or y0.dim() not in (2, 3) or y0.dtype != torch.float32:
+        raise ValueError("knockout_effects: y0 must be float32 [B, 1, %d] or [B, %d], got %s %s"
+                         % (N, N, y0.dtype, tuple(y0.shape)))
+    engine._require_gpu(params_of(odenet)[0], "odenet")
+    engine._require_gpu(y0, "y0")
+    device = y0.device
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # the scan's float64 grid
+    t = time_pts_to_project.to(device)
+    y0 = y0.detach().reshape(-1, 1, N)
+    B, G = y0.shape[0], len(genes)
+    k_max = max(1, min(int(genes_per_launch), G))
+    scores = torch.empty(G, dtype=torch.float32, device=device)
+    shift = torch.empty((G, N), dtype=torch.float32, device=device) if want_matrices else None
+    magnitude = torch.empty((G, N), dtype=torch.float32, device=device) if want_matrices else None
+    y0s = torch.empty((k_max, B, 1, N), dtype=torch.float32, device=device)
+    with torch.no_grad():
+        base = _calls_block(odenet, y0.unsqueeze(0), t, method=method, clamp=[-1]).contiguous()      # [T, B, N]
+        for k0 in range(0, G, k_max):
+            batch = genes[k0:k0 + k_max]
+            for j, this_gene in enumerate(batch):
+                y0s[j].copy_(y0)
+                y0s[j, :, 0, this_gene] = values[k0 + j]
+            sol = _calls_block(odenet, y0s[:len(batch)], t, method=method, clamp=batch)      # [T, k*B, N]
+            engine.knockout_effects(base, sol, batch, scores=scores[k0:k0 + len(batch)],
+                                    shift=shift[k0:k0 + len(batch)] if want_matrices else None,
+                                    magnitude=magnitude[k0:k0 + len(batch)] if want_matrices else None)
+            del sol       # one output block alive at a time
+    return KnockoutEffects(genes, scores.cpu().numpy(), shift, magnitude)
+
+
 def effects_matrix(odenet, rows=None, out=None):
     """The reference's regulatory "effects matrix" (extract_model_matrix_PHOENIX.py:46-58) on the device:
     effects[i, j] = relu(g_j) * (Ws^T Wa[:, :H]^T + Wp^T Wa[:, H:]^T)[i, j], regulator i -> target j, float32 [R, N].

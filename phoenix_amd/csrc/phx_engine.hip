@@ -1033,6 +1033,8 @@ struct SolveCall {
     int K = 0;           // ... and the grid steps per trajectory it holds (D1::K)
     int Bcall = 0;       // > 0: the batch is calls of Bcall trajectories, a launch takes whole calls (D1::Bcall); with
                          // o->t_per_sample t is [calls, T], one row per call
+    const int *clamp = nullptr;   // phx_odeint_clamped: the frozen gene of every call (device, [B / Bcall]); the launches'
+                                  // lists are offset together with their time rows
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1072,6 +1074,10 @@ int run_solve(const Pick &k, int cus, const SolveCall &c)
         if (!plan_rows(be, cus, p->N, p->H, std::min(chunk, c.B - b0), c.T, control, o->method, c.Bcall, &d)) return PHX_ERR_BAD_ARG;
         d.K = c.K;
         d.BN = (long long)c.B * p->N;   // time stride of the caller's [T,B,N] arrays
+        // a clamped launch of ONE call (calls == 1, or the remainder of a chunked batch) is planned like an ordinary
+        // shared-control launch and still runs the CALLS form, which alone reads the list: one group of Bcall rows
+        if (c.clamp && d.Bcall == 0) d.Bcall = c.Bcall;
+        a.clamp = c.clamp ? c.clamp + (c.Bcall > 0 ? b0 / c.Bcall : 0) : nullptr;
         const long long r0 = (long long)b0 * p->N;
         auto rows = [&](auto *q) { return q ? q + r0 : q; };
         a.t = !o->t_per_sample ? c.t   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
@@ -1761,6 +1767,44 @@ size_t phx_odeint_calls_grids_workspace_bytes(int N, int H, int B, int T, int ca
     const int cus = cus_or_mi355x(num_cus()), Bc = B / calls;
     const Pick k = pick_calls(true, cus, N, H, Bc, calls, T, method);
     return k.be ? launches_bytes(*k.be, cus, N, H, B, k.chunk, T, PHX_CTRL_SHARED, method, false, Bc) : 0;
+}
+
+// the kernel of the third generation that plans `calls` dopri5 calls with a time row each, or none (pick_calls' answer)
+static Pick pick_clamped(int cus, int N, int H, int B, int T, int calls)
+{
+    if (N <= 0 || H <= 0 || B <= 0 || T < 0 || calls < 1 || B % calls != 0) return {nullptr, 0};
+    const Pick k = pick_calls(true, cus, N, H, B / calls, calls, T, PHX_DOPRI5);
+    return (k.be && (k.be->id == 3 || k.be->id == 4)) ? k : Pick{nullptr, 0};
+}
+
+size_t phx_odeint_clamped_workspace_bytes(int N, int H, int B, int T, int calls)
+{
+    const int cus = cus_or_mi355x(num_cus());
+    const Pick k = pick_clamped(cus, N, H, B, T, calls);
+    return k.be ? launches_bytes(*k.be, cus, N, H, B, k.chunk, T, PHX_CTRL_SHARED, PHX_DOPRI5, false, B / calls) : 0;
+}
+
+int phx_odeint_clamped(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
+                       const int *clamp_gene, float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
+                       size_t workspace_bytes, void *stream)
+{
+    if (bad_params(p) || !y0_all || !t_all || !o || !clamp_gene || !sol_all || !status_all || !nfe_all || !nsteps_all ||
+        B <= 0 || T < 1 || !workspace)
+        return PHX_ERR_BAD_ARG;
+    if (o->method != PHX_DOPRI5 || o->control != PHX_CTRL_SHARED || !o->t_per_sample || o->calls < 1 || B % o->calls != 0)
+        return PHX_ERR_BAD_ARG;
+    // planned for the MI355X where no device is in sight, like the size query: a shape that no third-generation kernel
+    // plans is refused before the device is asked for anything
+    if (!pick_clamped(cus_or_mi355x(0), p->N, p->H, B, T, o->calls).be) return PHX_ERR_BAD_ARG;
+    const int cus = num_cus();
+    if (cus <= 0) return PHX_ERR_LAUNCH;
+    const Pick k = pick_clamped(cus, p->N, p->H, B, T, o->calls);
+    if (!k.be) return PHX_ERR_BAD_ARG;
+    SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
+                workspace, workspace_bytes, (hipStream_t)stream};
+    c.Bcall = B / o->calls;
+    c.clamp = clamp_gene;
+    return run_solve(k, cus, c);
 }
 
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,

@@ -174,6 +174,7 @@ struct SolveArgs {
     int grads;            // backward: 1 = parameter gradients wanted
     long long PP;         // backward: Regions::pp
     float *ckpt;          // k1_solve_bp: checkpoint region [D1::K][rows of the launch][N] (null: none)
+    const int *clamp;     // phx_odeint_clamped: the frozen gene of each call of the launch (device, [D1::TG]); null: none
 };
 
 // what a launch is planned for: the CUs that must hold its workgroups at once, the batch of B rows with T time points,
@@ -224,5 +225,10 @@ const Backend &adj3c_backend();
 // k1_solve_bp (backpropagation through the fixed-grid steps): not in the lists of the adjoint direction, it has entry
 // points of its own
 const Backend &bp_backend();
+
+// the CALLS + CLAMP forms of k1_solve_fwd3 / k1_solve_fwd3c (phx_odeint_clamped), compiled in units of their own
+// (phx_fwd3k.hip, phx_fwd3ck.hip) so that the parallel build is no longer than before
+const void *fwd3_clamp_kernel(bool half);
+const void *fwd3c_clamp_kernel(int nbt, bool half, bool hb);
 
 }  // namespace phxh

@@ -514,6 +514,56 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
     return sol, stats[0], stats[1], stats[2]
 
 
+OP_CLAMPED = 11      # workspace-size key of solve_forward_clamped (phx_odeint_clamped_workspace_bytes sizes it)
+
+
+def clamped_plan_exists(N, H, B, T, calls):
+    """whether phx_odeint_clamped serves `calls` dopri5 calls of B // calls rows (k1_solve_fwd3 / k1_solve_fwd3c plan
+    them); the size is remembered per shape and plan-switch setting"""
+    key = (OP_CLAMPED, N, H, B, T, calls) + _plan_env()
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _ws_bytes[key] = _lib.load().phx_odeint_clamped_workspace_bytes(N, H, B, T, calls)
+    return nbytes
+
+
+def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps=0, stats=None):
+    """`solve_forward` for dopri5 under shared control with calls = len(clamp) and one grid per call (t64 [calls, T]),
+    where call k holds gene clamp[k] at its initial value (phx_odeint_clamped; an int32 device tensor, -1: none).
+    ValueError where no third-generation kernel plans the calls -- solve them one by one on parameters whose g[gene]
+    is zeroed."""
+    B, N = y0.shape
+    calls = clamp.numel()
+    if clamp.dtype != torch.int32 or clamp.device != y0.device or not clamp.is_contiguous():
+        raise ValueError("solve_forward_clamped: clamp must be a contiguous int32 tensor on y0's device")
+    if calls < 1 or B % calls or t64.dim() != 2 or t64.shape[0] != calls:
+        raise ValueError("solve_forward_clamped: B divisible by the calls, t of shape [calls, T]")
+    T = t64.shape[-1]
+    nb = clamped_plan_exists(p.N, p.H, B, T, calls)
+    if nb == 0:
+        raise ValueError("a batch of %d clamped calls x %d trajectories cannot be planned for N=%d, H=%d" %
+                         (calls, B // calls, N, p.H))
+    sol = torch.empty((T, B, N), dtype=torch.float32, device=y0.device)
+    if stats is None:
+        stats = torch.empty((3, B), dtype=torch.int32, device=y0.device)
+    p.on_current_stream()
+    # the solve workspace of the stream, shared with solve_forward (one launch at a time uses it)
+    key = (y0.device.index, _stream_raw(y0.device.index), _lib.OP_ODEINT)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < nb:
+        ws = _ws_cache[key] = torch.empty(int(nb * 1.25) + 1024, dtype=torch.uint8, device=y0.device)
+        _ws_last.pop(key, None)
+    pkey = ("clamped", p.N, p.H, B, T, calls) + _plan_env()
+
+    def call(keep):
+        o = _opts("dopri5", _lib.CTRL_SHARED, rtol, atol, 1, t_is_f32, max_num_steps, calls, keep)
+        return _lib.load().phx_odeint_clamped(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(clamp), _p(sol),
+                                              _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
+
+    _solve_call(_lib.OP_ODEINT, pkey, y0.device, call)
+    return sol, stats[0], stats[1], stats[2]
+
+
 def solve_adjoint(p, t64, y_saved, grad_y, method, control, rtol, atol, t_per_sample, t_is_f32, want_grads=True,
                   max_num_steps=0, stats=None, step_size=0.0):
     """y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps.  `stats`: an int32 [3,B] to use (rows contiguous).
@@ -625,6 +675,48 @@ def influence_scores(sol, pairs, B, genes, want_targets=False, scores=None, targ
     _check_call(_lib.load().phx_influence_scores(_p(sol), T, pairs, B, N, (C.c_int * pairs)(*genes), _p(scores), _p(targets),
                                                  _p(ws), nbytes, _stream_ptr()))
     return scores, targets
+
+
+OP_KNOCKOUT = 12     # workspace-cache key of knockout_effects (phx_knockout_effects_workspace_bytes sizes it)
+
+
+def knockout_effects(base, sol, genes, want_matrices=False, scores=None, shift=None, magnitude=None):
+    """phx_knockout_effects: base [T, B, N] (the unperturbed solve), sol [T, K*B, N] (K clamped calls of B rows, `genes[k]`
+    the clamped gene of call k) -> (scores [K], shift [K, N] or None, magnitude [K, N] or None), all on the device.
+    `scores` / `shift` / `magnitude`: contiguous float32 device tensors to write into instead of fresh ones (a row range
+    of a screen's result); passing one of the matrices implies that matrix."""
+    _require_gpu(base, "base")
+    _require_gpu(sol, "sol")
+    genes = [int(g) for g in genes]
+    K = len(genes)
+    if base.dim() != 3 or not base.is_contiguous() or base.dtype != torch.float32:
+        raise ValueError("knockout_effects: base must be a contiguous float32 [T, B, N] block, got %s" % (tuple(base.shape),))
+    T, B, N = base.shape
+    if (sol.dim() != 3 or not sol.is_contiguous() or sol.dtype != torch.float32 or sol.device != base.device or
+            tuple(sol.shape) != (T, K * B, N)):
+        raise ValueError("knockout_effects: sol must be a contiguous float32 [T, K*B, N] = %s block on base's device, got %s"
+                         % ((T, K * B, N), tuple(sol.shape)))
+    if scores is None:
+        scores = torch.empty(K, dtype=torch.float32, device=sol.device)
+    if want_matrices:
+        if shift is None:
+            shift = torch.empty((K, N), dtype=torch.float32, device=sol.device)
+        if magnitude is None:
+            magnitude = torch.empty((K, N), dtype=torch.float32, device=sol.device)
+    for name, x, numel in (("scores", scores, K), ("shift", shift, K * N), ("magnitude", magnitude, K * N)):
+        if x is not None:
+            _require_gpu(x, name)
+            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device or x.dtype != torch.float32:
+                raise ValueError("knockout_effects: `%s` must be a contiguous float32 tensor of %d elements on sol's device"
+                                 % (name, numel))
+    key = (OP_KNOCKOUT, T, K, B, N)
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _ws_bytes[key] = _lib.load().phx_knockout_effects_workspace_bytes(T, K, B, N)
+    ws = _analysis_workspace(OP_KNOCKOUT, nbytes, sol.device)
+    _check_call(_lib.load().phx_knockout_effects(_p(base), _p(sol), T, K, B, N, (C.c_int * K)(*genes), _p(scores), _p(shift),
+                                                 _p(magnitude), _p(ws), nbytes, _stream_ptr()))
+    return scores, shift, magnitude
 
 
 OP_EFFECTS = 6       # workspace-cache key of effects_matrix (phx_effects_workspace_bytes sizes it)

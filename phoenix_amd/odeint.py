@@ -239,10 +239,81 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
     return (out, nfe, nsteps) if return_stats else out
 
 
-def _calls_block(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
+def _clamp_list(clamp, K, N):
+    """`clamp` of odeint_calls as K Python ints in [-1, N), checked on the host before anything is launched"""
+    if torch.is_tensor(clamp):
+        if clamp.dim() != 1 or clamp.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise TypeError("odeint_calls: clamp must be a 1-D integer tensor or a sequence of ints, got %s %s"
+                            % (clamp.dtype, tuple(clamp.shape)))
+        clamp = clamp.tolist()
+    try:
+        clamp = list(clamp)
+    except TypeError:
+        raise TypeError("odeint_calls: clamp must be a sequence of %d ints" % K) from None
+    for g in clamp:
+        if isinstance(g, bool) or not hasattr(g, "__index__"):
+            raise TypeError("odeint_calls: clamp entries must be integers, got %r" % (g,))
+    clamp = [int(g) for g in clamp]
+    if len(clamp) != K:
+        raise ValueError("odeint_calls: clamp names %d genes for %d calls" % (len(clamp), K))
+    for g in clamp:
+        if g < -1 or g >= N:
+            raise ValueError("odeint_calls: clamp entry %d is not a gene of 0 .. %d (or -1: none)" % (g, N - 1))
+    return clamp
+
+
+def _clamped_block(func, y0s, t, rtol, atol, method, options, clamp):
+    """`_calls_block` with call k's gene clamp[k] held at its initial value (-1: none): one launch of
+    phx_odeint_clamped where dopri5 plans the calls on the third-generation kernels, else the K calls one by one on a
+    parameter set whose g[gene] is zeroed -- the model the clamped call is defined by."""
+    K = y0s.shape[0]
+    clamp = _clamp_list(clamp, K, params_of(func)[0].shape[1])      # first: a bad list is refused whatever else holds
+    grids = torch.is_tensor(t) and t.ndimension() == 2
+    if grids and t.shape[0] != K:
+        raise ValueError("odeint_calls: t must be [T] or [K, T] with K = %d calls, got %s" % (K, tuple(t.shape)))
+    y0, t, rtol, atol, method, options = _check_inputs(func, y0s, t, rtol, atol, method, options)
+    params, y2, t1, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t[0] if grids else t, options)
+    if per_sample or control != _lib.CTRL_SHARED:
+        raise ValueError("odeint_calls: one shared time grid per call, batch_control='shared'")
+    # the grid as K rows, in the dtype the engine reads (a 1-D grid is expanded to K equal rows)
+    tK = t.detach().to(device=y0.device, dtype=t1.dtype)
+    tK = (tK if grids else tK.reshape(1, -1).expand(K, -1)).contiguous()
+    T = tK.shape[-1]
+    max_steps = int(options.get("max_num_steps", 0))
+    engine.check_pending_status()
+    if method == "dopri5" and engine.clamped_plan_exists(N, params[0].shape[0], B, T, K):
+        p = engine.params_cached(*params)
+        genes = torch.tensor(clamp, dtype=torch.int32).to(y0.device)
+        sol, status, _, _ = engine.solve_forward_clamped(p, y2.detach().contiguous(), tK, genes, rtol, atol, t_is_f32,
+                                                         max_steps)
+        engine.raise_for_status(status)
+        return sol
+    # one by one: the caller's module is never modified, the zeroed multiplier lives in a clone
+    ws, bs, wp, bp, wa, g = params
+    Bc = B // K
+    y2 = y2.detach().contiguous()
+    block = torch.empty((T, K, Bc, N), dtype=torch.float32, device=y0.device)
+    with torch.no_grad():
+        for k in range(K):
+            if clamp[k] < 0:
+                p = engine.params_cached(*params)
+            else:
+                gk = g.detach().clone()
+                gk.reshape(-1)[clamp[k]] = 0.0
+                p = engine.Params(ws, bs, wp, bp, wa, gk)
+            one, status, _, _ = engine.solve_forward(p, y2[k * Bc:(k + 1) * Bc], tK[k], method, control, rtol, atol, False,
+                                                     t_is_f32, max_steps, step_size=options.get("step_size", 0.0))
+            engine.raise_for_status(status)
+            block[:, k] = one
+    return block.reshape(T, K * Bc, N)
+
+
+def _calls_block(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None, clamp=None):
     """the solves of `odeint_calls` as the engine's own output block: [T, K*B, N], call k in rows k*B .. (k+1)*B - 1 of
     every output time (B = trajectories of one call).  One batched launch where the plan exists; else the K calls one by
-    one, copied into the same layout."""
+    one, copied into the same layout.  clamp: `_clamped_block`."""
+    if clamp is not None:
+        return _clamped_block(func, y0s, t, rtol, atol, method, options, clamp)
     K = y0s.shape[0]
     grids = torch.is_tensor(t) and t.ndimension() == 2
     if grids and t.shape[0] != K:
@@ -284,7 +355,7 @@ def _calls_block(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     return sol
 
 
-def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
+def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None, clamp=None):
     """K forward-only `odeint(func, y0s[k], t, ...)` calls in as few launches as the device has room for:
         y0s [K, *shape] (shape = [B,1,N] or [B,N]), t [T]  ->  [K, T, *shape]  (a view of the engine's [T, K*B, N]).
     t [K, T]: one time grid per call, `odeint(func, y0s[k], t[k], ...)` -- the validation loop of train_insilico.py:77-106;
@@ -292,9 +363,15 @@ def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None):
     Every call keeps the reference's batch semantics -- ONE adaptive step size shared by its B trajectories, chosen
     from its own error norm -- so the result equals the K separate calls (the analysis loop of
     find_gene_influences.py:64-77 issues 2 per gene).  Falls back to K launches where the batched plan does not
-    exist (shapes served by the VALU engine)."""
+    exist (shapes served by the VALU engine).
+    clamp (K ints, a sequence or an integer tensor; -1: none): call k holds gene clamp[k] at its initial value for the
+    whole time course, d y[:, clamp[k]] / dt = 0 -- level 0 is a knockout, a high level an over-expression.  Exactly the
+    solve of the model whose gene_multipliers[clamp[k]] is 0 (odenet.py:85-91).  dopri5 calls that the third-generation
+    kernels plan run in one launch (phx_odeint_clamped); every other case (a fixed-grid method, step_size, the VALU
+    engine, calls of more rows than those kernels plan) runs the K calls one by one on a cloned multiplier vector with
+    that entry zeroed; the module is never modified.  The list is range-checked on the host before any launch."""
     K = y0s.shape[0]
-    sol = _calls_block(func, y0s, t, rtol, atol, method, options)
+    sol = _calls_block(func, y0s, t, rtol, atol, method, options, clamp=clamp)
     return sol.reshape((sol.shape[0], K) + tuple(y0s.shape[1:])).transpose(0, 1)
 
 
