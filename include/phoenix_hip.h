@@ -319,6 +319,32 @@ int phx_hill_jacobian(const int *code, const int *off, const int *len, const flo
                       const int *ereg, const float *x, int B, int N, long long E, int mode, float *out, void *workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Knockout screens of that simulator (additive, ABI 7): the truth a model's knockout screen (phx_odeint_clamped +
+ * phx_knockout_effects) is scored against.  K calls of B rows all start from the SAME x0 [B, N], which is read once per call
+ * and not replicated; call k integrates the system with x[:, genes_host[k]] HELD at values_host[k] -- the column starts at
+ * the level and its rate is 0 in every stage, so it keeps the level bit for bit; genes_host[k] == -1 is the unperturbed
+ * call.  out [T, K * B, N]: row k * B + b of every time slice belongs to call k (the sol layout of phx_knockout_effects,
+ * which scores the block unchanged); out[0] is x0 with the clamped column replaced.  The integrator is phx_hill_simulate's:
+ * classical RK4, nsub = max(1, ceil(|span| / dt_max)) equal sub-steps per interval, h = (float)(span / nsub), fp32 state in
+ * LDS, fAct continued by 0 at TF <= 0; times [T] (DEVICE, double) may increase or decrease.
+ * One workgroup integrates a group of up to KPT calls of one sample: a thread walks its gene's program once per stage and
+ * applies every instruction to the KPT operand stacks.  A slot's arithmetic does not depend on the other slots, and a slot
+ * without a call integrates the unperturbed system and stores nothing (no remainder path): the bits of call k are the same
+ * whether it runs alone, first or last in a group, beside a duplicate of itself or in a remainder group, so a gene the
+ * clamped gene cannot reach has a shift of exactly 0 against the -1 call.  KPT = 2 up to 4 096 genes and 1 above: 2 measured
+ * fastest of 1, 2, 4, 8 on the shipped 350-gene network (profiles/hill_knockouts.json), and KPT x (genes per thread) <= 8.
+ * phx_debug_hill_knockouts_kpt(N): the KPT a call uses at N genes (0: N refused); PHX_HILLKO_KPT = 1 | 2 | 4 | 8 in the
+ * environment asks for another one, cut to that budget (tools/bench_hill_knockouts.py times them).
+ * genes_host / values_host [K] are HOST arrays: checked before any device call and handed to the kernel as launch
+ * arguments, 256 calls per launch.  Groups and rows are strided over capped grid dimensions: neither K nor B is bounded by
+ * one.  Nothing allocates, copies from pageable memory or synchronises.
+ * PHX_ERR_BAD_ARG with nothing launched: a null pointer, B / N / K / T < 1, dt_max not > 0, N > 8 192, a gene outside
+ * -1 .. N - 1, a level that is not finite, K * B beyond int. */
+int phx_hill_knockouts(const int *code, const int *off, const int *len, const float *consts, const float *x0,
+                       const double *times, int T, double dt_max, const int *genes_host, const float *values_host, int K,
+                       float *out, int B, int N, void *stream);
+int phx_debug_hill_knockouts_kpt(int N);
+
 /* the scoring tail of the gene-influence scan (find_gene_influences.py:64-77) on the solver's
  * own output.  sol [T, 2 * pairs * B, N] is the block phx_odeint wrote for 2 * pairs calls of B rows (opts->calls): call
  * 2j is the unperturbed solve of pair j, call 2j + 1 the perturbed one; genes_host [pairs] (HOST) names the perturbed

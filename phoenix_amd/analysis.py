@@ -461,6 +461,68 @@ def jacobian_recovery(odenet, system, x, diagonal=False):
     return JacobianRecovery(len(keep), *scores, jac.regulator[at], jac.target[at], true, learned)
 
 
+# ------------------------------------------------------------------ recovery of the simulator's knockout screen
+KnockoutRecoveryScores = collections.namedtuple("KnockoutRecoveryScores", ("n_entries", "sign_agreement", "pearson", "spearman",
+                                                                           "slope", "per_gene"))
+KnockoutPerGene = collections.namedtuple("KnockoutPerGene", ("n_entries", "sign_agreement", "pearson", "spearman", "slope"))
+KnockoutRecovery = collections.namedtuple("KnockoutRecovery", ("genes", "n_entries", "sign_agreement", "pearson", "spearman",
+                                                               "slope", "per_gene", "scores_spearman", "true", "learned"))
+
+
+def knockout_recovery_scores(genes, true_shift, learned_shift, min_effect=0.0):
+    """`recovery_scores` of two knockout screens' shift matrices ([G, N], tensors or arrays; float64 on the host).  Entry
+    (i, n) counts iff n != genes[i] (the held gene itself is no prediction) and |true_shift[i, n]| > min_effect (with the
+    default 0: the genes the held gene reaches at all -- the truth is exactly 0 elsewhere).  Returns
+    KnockoutRecoveryScores(n_entries, sign_agreement, pearson, spearman, slope, per_gene): the four statistics pooled over
+    the counted entries, and per_gene = KnockoutPerGene(n_entries int64 [G], sign_agreement, pearson, spearman, slope
+    float64 [G]), the same over the counted entries of each knockout.  A statistic that is not defined is NaN, as there:
+    every one of a knockout (or a screen) without a counted entry."""
+    t, l = _host_array(true_shift).astype(np.float64), _host_array(learned_shift).astype(np.float64)
+    genes = [int(g) for g in genes]
+    if t.ndim != 2 or t.shape != l.shape or t.shape[0] != len(genes):
+        raise ValueError("knockout_recovery_scores: true_shift and learned_shift must both be [%d, N], got %s and %s"
+                         % (len(genes), t.shape, l.shape))
+    G, N = t.shape
+    for g in genes:
+        if g < 0 or g >= N:
+            raise ValueError("knockout_recovery_scores: gene %d is not one of 0 .. %d" % (g, N - 1))
+    if not float(min_effect) >= 0:
+        raise ValueError("knockout_recovery_scores: min_effect must be >= 0, got %r" % (min_effect,))
+    counted = np.abs(t) > float(min_effect)
+    counted[np.arange(G), genes] = False
+    per = np.full((G, 4), np.nan)
+    for i in range(G):
+        per[i] = recovery_scores(t[i, counted[i]], l[i, counted[i]])
+    n_each = counted.sum(axis=1).astype(np.int64)
+    return KnockoutRecoveryScores(int(n_each.sum()), *recovery_scores(t[counted], l[counted]),
+                                  KnockoutPerGene(n_each, per[:, 0].copy(), per[:, 1].copy(), per[:, 2].copy(), per[:, 3].copy()))
+
+
+def knockout_recovery(odenet, system, y0, genes=None, value=0.0, time_pts_to_project=None, method="dopri5", dt_max=0.01,
+                      min_effect=0.0, genes_per_launch=8):
+    """Does a model trained on in-silico data predict what the simulator does under a knockout?  The model's screen,
+    `knockout_effects(odenet, y0, genes, value, time_pts_to_project, method, genes_per_launch)`, is held against the truth,
+    `system.knockout_effects` (a `HillSystem`: the same states, genes, levels and time points, integrated with sub-steps <=
+    dt_max), by `knockout_recovery_scores` on the two shift matrices.  Returns KnockoutRecovery(genes, n_entries,
+    sign_agreement, pearson, spearman, slope, per_gene, scores_spearman, true, learned): the pooled statistics and those of
+    every knockout; scores_spearman, the Spearman correlation of the two per-gene score vectors -- does the model rank the
+    influential genes as the truth does, which is what `pathway_permutation_test` feeds on; and the two KnockoutEffects.
+    Where `jacobian_recovery` asks about local slopes, this asks about the response to a sustained intervention.
+    ValueError before any launch when the model's gene count is not `system.N`."""
+    N = params_of(odenet)[0].shape[1]
+    if N != system.N:
+        raise ValueError("knockout_recovery: the model has %d genes, the system %d" % (N, system.N))
+    genes, values = _knockout_args(N, genes, value, genes_per_launch)
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))
+    learned = knockout_effects(odenet, y0, genes, values, time_pts_to_project, method, genes_per_launch)
+    true = system.knockout_effects(y0, genes, values, time_pts_to_project, dt_max)
+    s = knockout_recovery_scores(genes, true.shift, learned.shift, min_effect)
+    a, b = np.asarray(true.scores, np.float64), np.asarray(learned.scores, np.float64)
+    return KnockoutRecovery(genes, s.n_entries, s.sign_agreement, s.pearson, s.spearman, s.slope, s.per_gene,
+                            _pearson(_average_ranks(a), _average_ranks(b)), true, learned)
+
+
 # ------------------------------------------------------------------ pathway permutation tests (SURVEY.md row 22)
 def consolidate_gene_scores(gene_names, scores):
     """One score per gene symbol from one score per array entry (create_permutation_test_files_aws.R:68-84).  An entry

@@ -14,6 +14,9 @@ reproduced here (its RNG draws are not recorded), which DESIGN.md states.
 The same programs are differentiated: `HillSystem.jacobian` (`phx_hill_jacobian`, `csrc/phx_hilljac.hip`) is the true
 Jacobian of the rates on its sparse pattern, the ground truth `analysis.jacobian_recovery` scores a trained model against;
 `jacobian_reference` restates it in numpy.
+And perturbed: `HillSystem.knockouts` (`phx_hill_knockouts`, `csrc/phx_hillko.hip`) integrates the system with a gene held
+at a level, `HillSystem.knockout_effects` scores such a screen as `analysis.knockout_effects` scores the model's -- the
+ground truth of `analysis.knockout_recovery`; `rates_reference` / `knockouts_reference` restate them in numpy (section 8j).
 """
 import ast
 import collections
@@ -288,6 +291,45 @@ JACOBIAN_MODES = {None: 0, "mean": 1, "mean_abs": 2}     # `mode` of phx_hill_ja
 OP_HILL_JACOBIAN = 11    # workspace-cache key of HillSystem.jacobian (phx_hill_jacobian_workspace_bytes sizes it)
 
 
+def _knockout_args(name, N, genes, value, lowest):
+    """(genes, values) of a knockout screen of the simulator as lists of ints in lowest .. N - 1 and finite floats"""
+    genes = list(range(N)) if genes is None else list(genes.tolist() if hasattr(genes, "tolist") else genes)
+    for g in genes:
+        if isinstance(g, bool) or not hasattr(g, "__index__"):
+            raise TypeError("%s: genes must be integers, got %r" % (name, g))
+    genes = [int(g) for g in genes]
+    for g in genes:
+        if g < lowest or g >= N:
+            raise ValueError("%s: gene %d is not one of %d .. %d" % (name, g, lowest, N - 1))
+    if not genes:
+        raise ValueError("%s: no gene to hold" % name)
+    values = value.tolist() if hasattr(value, "tolist") else value
+    if isinstance(values, (list, tuple)):
+        if len(values) != len(genes):
+            raise ValueError("%s: %d values for %d genes" % (name, len(values), len(genes)))
+        values = [float(v) for v in values]
+    else:
+        values = [float(values)] * len(genes)
+    for v in values:
+        if not np.isfinite(np.float32(v)):
+            raise ValueError("%s: level %r is not a finite float32" % (name, v))
+    return genes, values
+
+
+def _knockout_times(name, times, dt_max):
+    t64 = np.ascontiguousarray(_host_times(times), np.float64).reshape(-1)
+    if t64.size < 1:
+        raise ValueError("%s: no time point" % name)
+    dt_max = float(dt_max)
+    if not dt_max > 0:
+        raise ValueError("%s: dt_max must be positive, got %r" % (name, dt_max))
+    return t64, dt_max
+
+
+def _host_times(times):
+    return times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else np.asarray(times, np.float64)
+
+
 class HillSystem:
     """The compiled rate expressions of one regulatory network, resident on the device."""
 
@@ -350,6 +392,79 @@ class HillSystem:
                                                          C.c_double(dt_max), engine._p(out), x2.shape[0], self.N,
                                                          engine._stream_ptr()))
         return out
+
+    # ---- knockout screens
+    def _knockout_x0(self, name, x0):
+        """x0 of a knockout screen as a contiguous float32 [B, N] tensor on the system's device"""
+        N = self.N
+        if not isinstance(x0, torch.Tensor):
+            raise TypeError("%s: x0 must be a tensor on the GPU, got %s" % (name, type(x0).__name__))
+        if (x0.dtype != torch.float32 or x0.shape[0] < 1 or
+                not ((x0.dim() == 2 and x0.shape[1] == N) or (x0.dim() == 3 and x0.shape[1:] == (1, N)))):
+            raise ValueError("%s: x0 must be float32 [B, %d] or [B, 1, %d], got %s %s" % (name, N, N, x0.dtype, tuple(x0.shape)))
+        engine._require_gpu(x0, "x0")
+        if self.device.type != "cuda" or x0.device != self.code.device:
+            raise ValueError("%s: x0 is on %s, the system on %s" % (name, x0.device, self.device))
+        return x0.detach().reshape(x0.shape[0], N).contiguous()
+
+    def _knockouts(self, x2, t64, genes, values, dt_max):
+        """phx_hill_knockouts on checked arguments: x2 [B, N], t64 [T] float64 on the device -> [T, K * B, N]"""
+        K, B = len(genes), x2.shape[0]
+        out = torch.empty((t64.numel(), K * B, self.N), dtype=torch.float32, device=x2.device)
+        engine._check_call(_lib.load().phx_hill_knockouts(*self._args(), engine._p(x2), engine._p(t64), t64.numel(),
+                                                          C.c_double(dt_max), (C.c_int * K)(*genes), (C.c_float * K)(*values), K,
+                                                          engine._p(out), B, self.N, engine._stream_ptr()))
+        return out
+
+    def knockouts(self, x0, times, genes, value=0.0, dt_max=0.01):
+        """`simulate` with a gene HELD at a level: states [T, K, B, N] float32 on the device, [:, k] the time course of the
+        system started from x0 ([B, N] or [B, 1, N], float32, on the device) with column genes[k] set to value[k] and kept
+        there -- its rate is 0 in every stage of every step, whatever its expression says (an "input gene" with that level).
+        genes: K ints in -1 .. N - 1, -1 the unperturbed system; value: a scalar or [K] finite levels, 0 a knockout, a high
+        level an over-expression.  The K calls share x0 (it is not replicated) and run in one pass (phx_hill_knockouts,
+        include/phoenix_hip.h): `simulate`'s integrator, several calls of a sample per workgroup.  A call's bits do not depend
+        on the calls beside it, so a gene that genes[k] does not reach (`jacobian_pattern`) equals the -1 call exactly.
+        Argument errors are raised on the host before any launch."""
+        genes, values = _knockout_args("knockouts", self.N, genes, value, lowest=-1)
+        t64, dt_max = _knockout_times("knockouts", times, dt_max)
+        x2 = self._knockout_x0("knockouts", x0)
+        out = self._knockouts(x2, torch.from_numpy(t64).to(x2.device), genes, values, dt_max)
+        return out.reshape(len(t64), len(genes), x2.shape[0], self.N)
+
+    def knockout_effects(self, x0, genes=None, value=0.0, times=None, dt_max=0.01, genes_per_launch=64, want_matrices=True):
+        """The knockout screen of `analysis.knockout_effects` on the simulator itself -- the truth of that screen for a model
+        trained on this system's data.  x0 [B, N] or [B, 1, N]: the states to start from; genes: the G genes to hold, one at
+        a time (default: all N); value: a scalar or [G] levels; times: default the model screen's arange(0, 1, 0.1).
+        The unperturbed system is a -1 call of `knockouts`; per block of `genes_per_launch` genes one `knockouts` pass and
+        one pass of phx_knockout_effects against that baseline; one output block is alive at a time.
+        Returns KnockoutEffects(genes, scores [G] float32 numpy, shift [G, N], magnitude [G, N] device tensors or None) with
+        the meaning they have there: over the times after the first and the B states, shift[i, n] is the mean of held -
+        baseline of gene n, magnitude[i, n] of its absolute value, scores[i] the mean of magnitude[i, n] over n != genes[i].
+        Both are exactly 0 at a gene that genes[i] does not reach."""
+        from .analysis import KnockoutEffects
+        N = self.N
+        genes, values = _knockout_args("knockout_effects", N, genes, value, lowest=0)
+        if isinstance(genes_per_launch, bool) or not hasattr(genes_per_launch, "__index__") or int(genes_per_launch) < 1:
+            raise ValueError("knockout_effects: genes_per_launch must be a positive integer")
+        t64, dt_max = _knockout_times("knockout_effects", np.arange(0, 1, 0.1) if times is None else times, dt_max)
+        if len(t64) < 2 or N < 2:
+            raise ValueError("knockout_effects: needs at least two time points and two genes")
+        x2 = self._knockout_x0("knockout_effects", x0)
+        device, B, G, T = x2.device, x2.shape[0], len(genes), len(t64)
+        k_max = min(int(genes_per_launch), G)
+        t_dev = torch.from_numpy(t64).to(device)
+        scores = torch.empty(G, dtype=torch.float32, device=device)
+        shift = torch.empty((G, N), dtype=torch.float32, device=device) if want_matrices else None
+        magnitude = torch.empty((G, N), dtype=torch.float32, device=device) if want_matrices else None
+        base = self._knockouts(x2, t_dev, [-1], [0.0], dt_max)                     # [T, B, N]
+        for k0 in range(0, G, k_max):
+            batch = genes[k0:k0 + k_max]
+            sol = self._knockouts(x2, t_dev, batch, values[k0:k0 + k_max], dt_max)     # [T, k * B, N]
+            engine.knockout_effects(base, sol, batch, scores=scores[k0:k0 + len(batch)],
+                                    shift=shift[k0:k0 + len(batch)] if want_matrices else None,
+                                    magnitude=magnitude[k0:k0 + len(batch)] if want_matrices else None)
+            del sol       # one output block alive at a time
+        return KnockoutEffects(genes, scores.cpu().numpy(), shift, magnitude)
 
     # ---- the true Jacobian
     def jacobian_pattern(self):
@@ -488,6 +603,102 @@ def jacobian_reference(system, x, dtype=np.float64, pattern=None):
                     val[-1], der[-1] = q, (ld - q[:, None] * rd) / r[:, None]
         out[:, e0:e1] = np.where(pushed[None, :], der[0], dtype(0))
     return out
+
+
+def _program_shapes(system):
+    """the programs of a system grouped by their opcode sequence: [(ops tuple, genes int64 [G], args int64 [len, G])];
+    genes of one shape are interpreted side by side"""
+    shapes = getattr(system, "_shapes", None)
+    if shapes is None:
+        by_ops = {}
+        for g in range(system.N):
+            o, n = int(system.off_host[g]), int(system.len_host[g])
+            if n:
+                by_ops.setdefault(tuple(system.code_host[o:o + n, 0].tolist()), []).append(g)
+        shapes = system._shapes = [
+            (ops, np.asarray(gs, np.int64),
+             np.stack([system.code_host[system.off_host[g]: system.off_host[g] + len(ops), 1] for g in gs], 1).astype(np.int64))
+            for ops, gs in by_ops.items()]
+    return shapes
+
+
+def rates_reference(system, x, dtype=np.float64):
+    """`HillSystem.rhs(x)` in numpy on the host, for a system on any device (device="cpu" included): the rates at the states
+    x [..., N] in `dtype`, "input gene" rows 0.  The value half of `jacobian_reference`'s interpreter -- the compiled programs
+    operation by operation, fAct continued by 0 at TF <= 0 -- with the genes whose programs have the same opcode sequence
+    evaluated side by side (the same elementwise arithmetic as gene by gene).  dtype=np.float32 rounds states and constants
+    first and runs every operation in float32."""
+    x = np.asarray(x, dtype)
+    if x.ndim < 1 or x.shape[-1] != system.N:
+        raise ValueError("x must be [..., %d], got %s" % (system.N, x.shape))
+    rows = x.reshape(-1, system.N)
+    consts = np.asarray(system.consts_host, dtype)
+    out = np.zeros_like(rows)
+    for ops, genes, args in _program_shapes(system):
+        st = []
+        for i, op in enumerate(ops):
+            a = args[i]
+            if op == 0:
+                st.append(np.broadcast_to(consts[a], (rows.shape[0], len(genes))))
+            elif op == 1:
+                st.append(rows[:, a])
+            elif op == 6:
+                st[-1] = -st[-1]
+            elif op == 7:
+                b, k, nn = consts[a], consts[a + 1], consts[a + 2]
+                tf, on = st[-1], st[-1] > 0
+                tn = np.where(on, np.where(on, np.abs(tf), dtype(1)) ** nn, dtype(0))
+                st[-1] = b * tn / (k + tn)
+            else:
+                r = st.pop()
+                l = st[-1]
+                st[-1] = l + r if op == 2 else l - r if op == 3 else l * r if op == 4 else l / r
+        out[:, genes] = st[0]
+    return out.reshape(x.shape)
+
+
+def knockouts_reference(system, x0, times, genes, values, dt_max, dtype=np.float64):
+    """`HillSystem.knockouts` in numpy on the host, for a system on any device: [T, K, B, N] in `dtype`.  A restatement of
+    the kernel's integrator on `rates_reference` -- classical RK4 in the kernel's order of operations, nsub = max(1,
+    ceil(|span| / dt_max)) equal sub-steps of h = dtype(span / nsub) per interval -- with the clamp: call k starts with
+    column genes[k] at values[k], and the rate of that column is replaced by 0 in every stage (genes[k] == -1: none).
+    x0 [B, N] or [B, 1, N]; genes / values: K ints in -1 .. N - 1 and K levels."""
+    N = system.N
+    x0 = np.asarray(x0, dtype)
+    if not ((x0.ndim == 2 and x0.shape[1] == N) or (x0.ndim == 3 and x0.shape[1:] == (1, N))) or x0.shape[0] < 1:
+        raise ValueError("x0 must be [B, %d] or [B, 1, %d], got %s" % (N, N, x0.shape))
+    genes, values = _knockout_args("knockouts_reference", N, genes, list(values), lowest=-1)
+    t64, dt_max = _knockout_times("knockouts_reference", times, dt_max)
+    K, B = len(genes), x0.shape[0]
+    y = np.repeat(x0.reshape(1, B, N), K, axis=0)
+    held = [(k, g) for k, g in enumerate(genes) if g >= 0]
+    for k, g in held:
+        y[k, :, g] = dtype(values[k])
+
+    def f(x):
+        r = rates_reference(system, x, dtype)
+        for k, g in held:
+            r[k, :, g] = 0
+        return r
+
+    out = [y.copy()]
+    half, one, two, six = dtype(0.5), dtype(1), dtype(2), dtype(6)
+    for i in range(len(t64) - 1):
+        span = t64[i + 1] - t64[i]
+        nsub = max(1, int(np.ceil(abs(span) / dt_max)))
+        h = dtype(span / nsub)
+        for _ in range(nsub):
+            k1 = f(y)
+            acc = one * k1
+            k2 = f(y + (half * h) * k1)
+            acc = acc + two * k2
+            k3 = f(y + (half * h) * k2)
+            acc = acc + two * k3
+            k4 = f(y + h * k3)
+            acc = acc + one * k4
+            y = y + (h / six) * acc
+        out.append(y.copy())
+    return np.stack(out)
 
 
 def generate_dataset(system, numsamples, time_stamps=(0.0, 2.0, 3.0, 7.0, 9.0), expnoise=0.0, dt_max=0.01, rng=None,
