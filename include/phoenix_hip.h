@@ -146,6 +146,18 @@ size_t phx_odeint_clamped_workspace_bytes(int N, int H, int B, int T, int calls)
 int phx_odeint_clamped(const phx_params *p, const float *y0, const double *t, int B, int T, const phx_solve_opts *opts,
                        const int *clamp_gene, float *sol, int *status, int *nfe, int *nsteps, void *workspace,
                        size_t workspace_bytes, void *stream);
+/* Combination knockouts (additive, ABI 7): phx_odeint_clamped with a SET of held genes per call.  clamp_genes is DEVICE,
+ * [calls, width] row-major, 1 <= width <= PHX_CLAMP_MAX: call k holds every gene of its row at its initial value for the
+ * whole time course -- exactly the solve of the model whose g is 0 on the set, arithmetic included (the sweeps compare a
+ * gene against the call's row, which a workgroup reads once, instead of against one index).  Entries no gene has
+ * (-1, >= N) match nothing and pad a shorter set; a gene named twice counts once; the list is not validated.  Planning,
+ * refusals and workspace (phx_odeint_clamped_workspace_bytes) are phx_odeint_clamped's, which is the width = 1 case; a
+ * batch that spans several launches has its list offset by width x calls together with the time rows and the y0 / sol
+ * rows.  PHX_ERR_BAD_ARG before any device call also for width < 1, width > PHX_CLAMP_MAX and a null list. */
+#define PHX_CLAMP_MAX 4
+int phx_odeint_clamped_sets(const phx_params *p, const float *y0, const double *t, int B, int T, const phx_solve_opts *opts,
+                            const int *clamp_genes, int width, float *sol, int *status, int *nfe, int *nsteps,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* Replaces ODENet.forward / prior_only_forward (odenet.py:85-98): out[B,N] = f(y[B,N]). */
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only,
@@ -379,6 +391,32 @@ size_t phx_knockout_effects_workspace_bytes(int T, int K, int B, int N);
 int phx_knockout_effects(const float *base, const float *sol, int T, int K, int B, int N, const int *genes_host,
                          float *scores, float *shift, float *magnitude, void *workspace, size_t workspace_bytes,
                          void *stream);
+
+/* The scoring pass of a PAIR screen: K calls that hold two genes each (phx_odeint_clamped_sets) against the unperturbed
+ * solve and the two single-gene calls of every pair.  base [T, B, N]; singles [T, G * B, N]: G single-gene calls, the sol
+ * layout of phx_knockout_effects, single g holding gene genes_host[g] (HOST, [G]); sol [T, K * B, N]: K pair calls, pair k
+ * holding the genes of singles ia_host[k] and ib_host[k] (HOST, [K], indices into the G singles).  All differences are
+ * float32, over tau = 1 .. T-1 and b < B, with d_x = x - base and e = d_ab - (d_a + d_b) (symmetric in a and b: swapping
+ * the pair changes no bit).  Every matrix is [K, N] and may be NULL:
+ *     shift[k, n]                 = mean of d_ab
+ *     magnitude[k, n]             = mean of |d_ab|
+ *     interaction[k, n]           = mean of e        the joint effect beyond the sum of the single ones (epistasis)
+ *     interaction_magnitude[k, n] = mean of |e|
+ *     scores[k]                   = mean of magnitude[k, n] over n not in {a, b}                (required)
+ *     interaction_scores[k]       = mean of interaction_magnitude[k, n] over n not in {a, b}    (required)
+ * The two held columns are skipped by index, not subtracted from a total (on column a, e is -d_b[a], no interaction, and
+ * it dominates the row), and reported in the matrices as computed.  sol and the singles are read once (their tau = 0 slabs
+ * not at all); every sum runs in an order fixed by (T, B, N) alone (no atomics): two calls agree bit for bit, with or
+ * without the optional outputs, and however the K pairs are split over calls.  Non-finite inputs propagate.
+ * PHX_ERR_BAD_ARG before any device call: null base / singles / sol / ia_host / ib_host / genes_host / scores /
+ * interaction_scores, T < 2, K < 1 (or > 65535), G < 2, B < 1, N < 3, an index outside [0, G), ia[k] == ib[k], a gene
+ * outside [0, N); PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_knockout_epistasis_workspace_bytes(T, K, G, B, N) (0 for a shape the call refuses): the sums live there. */
+size_t phx_knockout_epistasis_workspace_bytes(int T, int K, int G, int B, int N);
+int phx_knockout_epistasis(const float *base, const float *singles, const float *sol, int T, int K, int G, int B, int N,
+                           const int *ia_host, const int *ib_host, const int *genes_host, float *scores,
+                           float *interaction_scores, float *shift, float *magnitude, float *interaction,
+                           float *interaction_magnitude, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The explainability matrices of a trained model, regulator i -> target j (the orientation of effects_mat and of the
  * gene-influence matrix), from the engine layout as it is.  With s = y - 0.5 and r = relu(g):

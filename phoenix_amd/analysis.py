@@ -183,6 +183,127 @@ def knockout_effects(odenet, y0, genes=None, value=0.0, time_pts_to_project=None
     return KnockoutEffects(genes, scores.cpu().numpy(), shift, magnitude)
 
 
+KnockoutPairs = collections.namedtuple("KnockoutPairs", ("pairs", "genes", "scores", "interaction_scores", "shift", "magnitude",
+                                                        "interaction", "interaction_magnitude", "singles"))
+
+
+def _int_list(xs, what):
+    xs = list(xs.tolist() if hasattr(xs, "tolist") else xs)
+    for g in xs:
+        if isinstance(g, bool) or not hasattr(g, "__index__"):
+            raise TypeError("knockout_pairs: %s must be integers, got %r" % (what, g))
+    return [int(g) for g in xs]
+
+
+def _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch):
+    """(genes [G], values [G], pairs [K] of (a, b) genes, ia [K], ib [K] indices into genes) of `knockout_pairs`, checked
+    on the host before any launch"""
+    if genes is None and pairs is None:
+        raise ValueError("knockout_pairs: give `genes` (all their pairs) or `pairs`; all pairs of all %d genes are never "
+                         "implied" % N)
+    if pairs is not None:
+        pairs = [tuple(_int_list(p, "the genes of a pair")) for p in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
+        seen = set()
+        for p in pairs:
+            if len(p) != 2:
+                raise ValueError("knockout_pairs: a pair is two genes, got %r" % (p,))
+            if p[0] == p[1]:
+                raise ValueError("knockout_pairs: the pair (%d, %d) holds one gene twice" % p)
+            if frozenset(p) in seen:
+                raise ValueError("knockout_pairs: the pair (%d, %d) is listed twice" % p)
+            seen.add(frozenset(p))
+        if not pairs:
+            raise ValueError("knockout_pairs: no pair to hold")
+    if genes is None:
+        genes = sorted(set(g for p in pairs for g in p))
+    else:
+        genes = _int_list(genes, "genes")
+        if len(set(genes)) != len(genes):
+            raise ValueError("knockout_pairs: a gene is listed twice in `genes`")
+        if len(genes) < 2:
+            raise ValueError("knockout_pairs: a pair needs two genes, `genes` names %d" % len(genes))
+    for g in genes + [g for p in (pairs or []) for g in p]:
+        if g < 0 or g >= N:
+            raise ValueError("knockout_pairs: gene %d is not one of 0 .. %d" % (g, N - 1))
+    index = {g: i for i, g in enumerate(genes)}
+    if pairs is None:
+        pairs = [(genes[i], genes[j]) for i in range(len(genes)) for j in range(i + 1, len(genes))]
+    for p in pairs:
+        if p[0] not in index or p[1] not in index:
+            raise ValueError("knockout_pairs: the pair (%d, %d) names a gene that `genes` does not" % p)
+    values = value.tolist() if hasattr(value, "tolist") else value
+    if isinstance(values, (list, tuple)):
+        if len(values) != len(genes):
+            raise ValueError("knockout_pairs: %d values for %d genes" % (len(values), len(genes)))
+        values = [float(v) for v in values]
+    else:
+        values = [float(values)] * len(genes)
+    if isinstance(pairs_per_launch, bool) or not hasattr(pairs_per_launch, "__index__") or int(pairs_per_launch) < 1:
+        raise ValueError("knockout_pairs: pairs_per_launch must be a positive integer")
+    return genes, values, pairs, [index[p[0]] for p in pairs], [index[p[1]] for p in pairs]
+
+
+def knockout_pairs(odenet, y0, genes=None, pairs=None, value=0.0, time_pts_to_project=None, method="dopri5",
+                   pairs_per_launch=8, want_matrices=True, max_singles_bytes=4 << 30):
+    """Combination knockout screen: what does the system do when TWO genes are held together, and is the joint effect
+    more or less than the sum of the single ones (epistasis, synthetic lethality, combination targets)?
+    genes: G >= 2 distinct genes, all G (G - 1) / 2 pairs of them; or pairs: an explicit list of (a, b), a != b, no pair
+    twice in either order (`genes` is then their sorted union unless given, and must name every gene of a pair).  One of
+    the two must be given.  value: a scalar or one level per gene of `genes`; y0, time_pts_to_project, method as in
+    `knockout_effects`.
+    The baseline is solved once, the G single-gene calls once (width-1 sets in the clamped launches; that block,
+    4 T G B N bytes, stays alive -- beyond `max_singles_bytes` the call is refused), then per block of `pairs_per_launch`
+    pairs one clamped launch (`odeint_calls(clamp=[(a, b), ...])`) and one pass of phx_knockout_epistasis; one pair
+    block is alive at a time.
+    Returns KnockoutPairs(pairs, genes, scores, interaction_scores, shift, magnitude, interaction,
+    interaction_magnitude, singles): with d_x = x - baseline over the projected time points after the first and the B
+    states and e = d_ab - (d_a + d_b), shift / magnitude [K, N] are the means of d_ab / |d_ab|, interaction /
+    interaction_magnitude those of e / |e| (device tensors, or None), scores / interaction_scores [K] (float32 numpy) the
+    means of magnitude / interaction_magnitude over the targets n other than a and b, and `singles` the KnockoutEffects
+    of the G single screens.  An interaction is a second-order difference of four solves: on weakly coupled weights it
+    sits at the solver's tolerance."""
+    N = params_of(odenet)[0].shape[1]
+    genes, values, pairs, ia, ib = _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch)   # first, whatever else holds
+    if y0.shape[-1] != N or y0.dim() not in (2, 3) or y0.dtype != torch.float32:
+        raise ValueError("knockout_pairs: y0 must be float32 [B, 1, %d] or [B, %d], got %s %s"
+                         % (N, N, y0.dtype, tuple(y0.shape)))
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # the scan's float64 grid
+    G, K, T = len(genes), len(pairs), int(time_pts_to_project.shape[-1])
+    B = y0.numel() // N
+    if 4 * T * G * B * N > max_singles_bytes:
+        raise ValueError("knockout_pairs: the block of the %d single-gene solves takes 4 T G B N = %d bytes, more than "
+                         "max_singles_bytes = %d; screen fewer genes at a time" % (G, 4 * T * G * B * N, max_singles_bytes))
+    engine._require_gpu(params_of(odenet)[0], "odenet")
+    engine._require_gpu(y0, "y0")
+    device = y0.device
+    t = time_pts_to_project.to(device)
+    y0 = y0.detach().reshape(-1, 1, N)
+    k_max = max(1, min(int(pairs_per_launch), K))
+    out = [torch.empty(K, dtype=torch.float32, device=device) for _ in range(2)]
+    out += [torch.empty((K, N), dtype=torch.float32, device=device) if want_matrices else None for _ in range(4)]
+    with torch.no_grad():
+        base = _calls_block(odenet, y0.unsqueeze(0), t, method=method, clamp=[-1]).contiguous()      # [T, B, N]
+        y0s = y0.unsqueeze(0).repeat(G, 1, 1, 1)
+        for g in range(G):
+            y0s[g, :, 0, genes[g]] = values[g]
+        singles = _calls_block(odenet, y0s, t, method=method, clamp=genes).contiguous()              # [T, G*B, N]
+        one = engine.knockout_effects(base, singles, genes, want_matrices=want_matrices)
+        y0s = torch.empty((k_max, B, 1, N), dtype=torch.float32, device=device)
+        for k0 in range(0, K, k_max):
+            k1 = min(K, k0 + k_max)
+            for j in range(k1 - k0):
+                y0s[j].copy_(y0)
+                y0s[j, :, 0, pairs[k0 + j][0]] = values[ia[k0 + j]]
+                y0s[j, :, 0, pairs[k0 + j][1]] = values[ib[k0 + j]]
+            sol = _calls_block(odenet, y0s[:k1 - k0], t, method=method, clamp=pairs[k0:k1])          # [T, k*B, N]
+            engine.knockout_epistasis(base, singles, sol.contiguous(), ia[k0:k1], ib[k0:k1], genes,
+                                      out=[None if x is None else x[k0:k1] for x in out])
+            del sol       # one pair block alive at a time
+    return KnockoutPairs(pairs, genes, out[0].cpu().numpy(), out[1].cpu().numpy(), out[2], out[3], out[4], out[5],
+                         KnockoutEffects(genes, one[0].cpu().numpy(), one[1], one[2]))
+
+
 def effects_matrix(odenet, rows=None, out=None):
     """The reference's regulatory "effects matrix" (extract_model_matrix_PHOENIX.py:46-58) on the device:
     effects[i, j] = relu(g_j) * (Ws^T Wa[:, :H]^T + Wp^T Wa[:, H:]^T)[i, j], regulator i -> target j, float32 [R, N].

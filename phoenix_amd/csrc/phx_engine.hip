@@ -1033,8 +1033,9 @@ struct SolveCall {
     int K = 0;           // ... and the grid steps per trajectory it holds (D1::K)
     int Bcall = 0;       // > 0: the batch is calls of Bcall trajectories, a launch takes whole calls (D1::Bcall); with
                          // o->t_per_sample t is [calls, T], one row per call
-    const int *clamp = nullptr;   // phx_odeint_clamped: the frozen gene of every call (device, [B / Bcall]); the launches'
-                                  // lists are offset together with their time rows
+    const int *clamp = nullptr;   // phx_odeint_clamped_sets: the held genes of every call (device, [B / Bcall, clamp_width]);
+                                  // the launches' lists are offset together with their time rows
+    int clamp_width = 1;          // ... entries per call
 };
 
 // diagnostic kernel events (phx_debug_*_kernel_events): ONE pair around all solve launches of a call, closed early when
@@ -1077,7 +1078,8 @@ int run_solve(const Pick &k, int cus, const SolveCall &c)
         // a clamped launch of ONE call (calls == 1, or the remainder of a chunked batch) is planned like an ordinary
         // shared-control launch and still runs the CALLS form, which alone reads the list: one group of Bcall rows
         if (c.clamp && d.Bcall == 0) d.Bcall = c.Bcall;
-        a.clamp = c.clamp ? c.clamp + (c.Bcall > 0 ? b0 / c.Bcall : 0) : nullptr;
+        a.clamp = c.clamp ? c.clamp + (size_t)c.clamp_width * (c.Bcall > 0 ? b0 / c.Bcall : 0) : nullptr;
+        a.clamp_width = c.clamp_width;
         const long long r0 = (long long)b0 * p->N;
         auto rows = [&](auto *q) { return q ? q + r0 : q; };
         a.t = !o->t_per_sample ? c.t   // rows of b0 onward; the buffer holds floats when t_is_f32 == 2
@@ -1784,12 +1786,12 @@ size_t phx_odeint_clamped_workspace_bytes(int N, int H, int B, int T, int calls)
     return k.be ? launches_bytes(*k.be, cus, N, H, B, k.chunk, T, PHX_CTRL_SHARED, PHX_DOPRI5, false, B / calls) : 0;
 }
 
-int phx_odeint_clamped(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
-                       const int *clamp_gene, float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
-                       size_t workspace_bytes, void *stream)
+int phx_odeint_clamped_sets(const phx_params *p, const float *y0_all, const double *t_all, int B, int T,
+                            const phx_solve_opts *o, const int *clamp_genes, int width, float *sol_all, int *status_all,
+                            int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (bad_params(p) || !y0_all || !t_all || !o || !clamp_gene || !sol_all || !status_all || !nfe_all || !nsteps_all ||
-        B <= 0 || T < 1 || !workspace)
+    if (bad_params(p) || !y0_all || !t_all || !o || !clamp_genes || !sol_all || !status_all || !nfe_all || !nsteps_all ||
+        B <= 0 || T < 1 || !workspace || width < 1 || width > PHX_CLAMP_MAX)
         return PHX_ERR_BAD_ARG;
     if (o->method != PHX_DOPRI5 || o->control != PHX_CTRL_SHARED || !o->t_per_sample || o->calls < 1 || B % o->calls != 0)
         return PHX_ERR_BAD_ARG;
@@ -1803,8 +1805,17 @@ int phx_odeint_clamped(const phx_params *p, const float *y0_all, const double *t
     SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
                 workspace, workspace_bytes, (hipStream_t)stream};
     c.Bcall = B / o->calls;
-    c.clamp = clamp_gene;
+    c.clamp = clamp_genes;
+    c.clamp_width = width;
     return run_solve(k, cus, c);
+}
+
+int phx_odeint_clamped(const phx_params *p, const float *y0_all, const double *t_all, int B, int T, const phx_solve_opts *o,
+                       const int *clamp_gene, float *sol_all, int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
+                       size_t workspace_bytes, void *stream)
+{
+    return phx_odeint_clamped_sets(p, y0_all, t_all, B, T, o, clamp_gene, 1, sol_all, status_all, nfe_all, nsteps_all,
+                                   workspace, workspace_bytes, stream);
 }
 
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,

@@ -61,7 +61,7 @@ const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
     const char *et = getenv("PHX_V3_TERM");   // diagnostic: 0 = no terminal tiles, every step ends with the accept pass
     a.w.prof_level = (a.w.prof_level & 0xff) | ((et && et[0] == '0') ? FWD3_NO_TERM : 0);
     const bool split = v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1;   // small batch: the waves of a tile split its blocks
-    if (a.clamp) return d.Bcall > 0 ? fwd3_clamp_kernel(half) : nullptr;   // a frozen gene per call (phx_fwd3k.hip)
+    if (a.clamp) return d.Bcall > 0 ? fwd3_clamp_kernel(half) : nullptr;   // held genes per call (phx_fwd3k.hip)
     if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
         return half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false, true>)
                     : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, false, true>);
@@ -74,7 +74,7 @@ const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
 hipError_t launch_fwd3(const void *fn, const SolveArgs &a, hipStream_t st)
 {
     return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.y0, a.t, a.sol,
-                             a.status, a.nfe, a.nsteps, a.clamp);
+                             a.status, a.nfe, a.nsteps, a.clamp, a.clamp_width);
 }
 
 }  // namespace

@@ -54,7 +54,7 @@ const void *prepare_fwd3c(SolveArgs &a, const phx_params *p, hipStream_t st)
     // (tile, block) slots per wave the kernel is built for (unused slots of the eight-slot form cost a scalar branch each)
     const int nbt = d.TPW * d.NB <= 1 || d.split > 1 ? 1 : 8;
     const bool half = d.Hc <= 40;   // every chunk's last tile has at most 8 live rows (rho16, phx_mfma_v3common.inc)
-    if (a.clamp) return d.Bcall > 0 ? fwd3c_clamp_kernel(nbt, half, d.hb != 0) : nullptr;   // a frozen gene per call (phx_fwd3ck.hip)
+    if (a.clamp) return d.Bcall > 0 ? fwd3c_clamp_kernel(nbt, half, d.hb != 0) : nullptr;   // held genes per call (phx_fwd3ck.hip)
     if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
         switch (nbt * 2 + (half ? 1 : 0) + (d.hb ? 32 : 0)) {
         case 35: return reinterpret_cast<const void *>(k1_solve_fwd3c<1, true, true, true>);
@@ -77,7 +77,7 @@ const void *prepare_fwd3c(SolveArgs &a, const phx_params *p, hipStream_t st)
 hipError_t launch_fwd3c(const void *fn, const SolveArgs &a, hipStream_t st)
 {
     return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.y0, a.t, a.sol,
-                             a.status, a.nfe, a.nsteps, a.clamp);
+                             a.status, a.nfe, a.nsteps, a.clamp, a.clamp_width);
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // phx_fwd3ck.hip -- the CALLS + CLAMP forms of k1_solve_fwd3c (phx_mfma_fwd3c.inc): several shared-control calls per
-// launch, each with one gene held at its initial value (phx_odeint_clamped).  A translation unit of its own: the six forms
-// are compiled beside those of phx_fwd3c.hip instead of after them.  phx_fwd3c.hip plans, lays out and launches them.
+// launch, each with a set of up to PHX_CLAMP_MAX genes held at their initial values (phx_odeint_clamped_sets).  A
+// translation unit of its own: the six forms are compiled beside those of phx_fwd3c.hip instead of after them.
+// phx_fwd3c.hip plans, lays out and launches them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,7 +1,7 @@
 // phx_fwd3k.hip -- the CALLS + CLAMP forms of k1_solve_fwd3 (phx_mfma_fwd3.inc): several shared-control calls per launch,
-// each with one gene held at its initial value (phx_odeint_clamped).  A translation unit of its own: the forms are
-// compiled beside those of phx_fwd3.hip, with that unit's flags (phoenix_amd/build.py), instead of after them.
-// phx_fwd3.hip plans, lays out and launches them.
+// each with a set of up to PHX_CLAMP_MAX genes held at their initial values (phx_odeint_clamped_sets).  A translation
+// unit of its own: the forms are compiled beside those of phx_fwd3.hip, with that unit's flags (phoenix_amd/build.py),
+// instead of after them.  phx_fwd3.hip plans, lays out and launches them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

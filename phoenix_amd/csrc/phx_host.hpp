@@ -174,7 +174,9 @@ struct SolveArgs {
     int grads;            // backward: 1 = parameter gradients wanted
     long long PP;         // backward: Regions::pp
     float *ckpt;          // k1_solve_bp: checkpoint region [D1::K][rows of the launch][N] (null: none)
-    const int *clamp;     // phx_odeint_clamped: the frozen gene of each call of the launch (device, [D1::TG]); null: none
+    const int *clamp;     // phx_odeint_clamped_sets: the held genes of each call of the launch (device, [D1::TG, clamp_width]);
+                          // null: none
+    int clamp_width;      // ... and the entries per call (1 .. PHX_CLAMP_MAX)
 };
 
 // what a launch is planned for: the CUs that must hold its workgroups at once, the batch of B rows with T time points,

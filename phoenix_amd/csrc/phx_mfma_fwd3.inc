@@ -28,13 +28,15 @@ __host__ __device__ inline size_t ctlf3_bytes(int Bt, int ntg) { return ctl_byte
 // CALLS: the launch is d.TG independent odeint calls of d.Bcall rows under shared control (D1::Bcall, phx_solver.hpp):
 // batch group g is call g, it reads time row g when cfg.t_per_sample is set, and the rows of its last tile beyond
 // d.Bcall are padding (rowof).  A template flag, so that the instantiations of every other launch compile as before.
-// CLAMP (only with CALLS): call g holds gene clamp_gene[g] at its initial value -- the sweeps read relu(g) of that gene
-// as 0, so every stage slope of it is the g[gene] = 0 model's (phx_odeint_clamped); an index no gene has clamps nothing.
-// Without CLAMP the trailing argument is never read.
+// CLAMP (only with CALLS): call g holds the genes clamp_gene[g * clamp_width .. + clamp_width) (at most PHX_CLAMP_MAX) at
+// their initial values -- the sweeps read relu(g) of those genes as 0, so every stage slope of them is that of the model
+// with g = 0 on the set (phx_odeint_clamped_sets); an index no gene has clamps nothing and pads a set.
+// Without CLAMP the two trailing arguments are never read.
 template <int HT, int MAXT, bool HALF, bool SPLIT, bool CALLS = false, bool CLAMP = false>
 __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, SolveCfg cfg, const float *__restrict__ y0,
                                                       const double *__restrict__ t, float *sol, int *status,
-                                                      int *nfe_out, int *nsteps_out, const int *__restrict__ clamp_gene)
+                                                      int *nfe_out, int *nsteps_out, const int *__restrict__ clamp_gene,
+                                                      int clamp_width)
 {
     static_assert(!CLAMP || CALLS, "a clamped gene belongs to a call");
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -48,7 +50,8 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     // the caller's row of local row lb (B: none, a padding row), and the time row of a shared-control group
     auto rowof = [&](int lb) -> int { return CALLS ? (lb < d.Bcall ? grp * d.Bcall + lb : B) : grp * Bt + lb; };
     const int trow_sh = CALLS ? grp : 0;
-    const int cgene = CLAMP ? __builtin_amdgcn_readfirstlane(clamp_gene[grp]) : -1;   // the call's frozen gene
+    ClampSet cset{};   // the call's held genes
+    if constexpr (CLAMP) cset = clamp_set(clamp_gene, grp, clamp_width);
     constexpr int F2 = 2 * HT;
     // small batches: the waves of a tile split its gene blocks (v3_split_parts, phx_mfma_v3common.inc)
     // (SPLIT is a template flag: the large-batch instantiation compiles exactly as without this path -- as run-time branches it cost
@@ -439,7 +442,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                 if constexpr (CLAMP) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if ((blk0 + bl) * 32 + gmap(lq, j) == cgene) rr[j] = 0.f;
+                        if (clamp_holds(cset, (blk0 + bl) * 32 + gmap(lq, j))) rr[j] = 0.f;
                 }
 #ifdef PHX_PROF_BLOCKS
                 if (tm.on && prof_sweep) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tm.mark(12); }   // diagnostic: tile wait

@@ -32,11 +32,13 @@ __host__ __device__ inline size_t hsf_offset(int Bt, int ntg) { return (ctlf3c_b
 __host__ __device__ inline size_t spf_bytes(int ntg, int parts) { return (size_t)(parts - 1) * ntg * (2 * 3 * 1024 + 256); }
 
 // CALLS: as in k1_solve_fwd3 -- d.TG independent shared-control calls of d.Bcall rows, one batch group and one time row each
-// CLAMP (only with CALLS): as in k1_solve_fwd3 -- call g reads relu(g) of gene clamp_gene[g] as 0 in every sweep
+// CLAMP (only with CALLS): as in k1_solve_fwd3 -- call g reads relu(g) of its clamp_width genes of clamp_gene as 0 in
+// every sweep
 template <int NBT, bool HALF, bool HB, bool CALLS = false, bool CLAMP = false>
 __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, SolveCfg cfg, const float *__restrict__ y0,
                                                       const double *__restrict__ t, float *sol, int *status,
-                                                      int *nfe_out, int *nsteps_out, const int *__restrict__ clamp_gene)
+                                                      int *nfe_out, int *nsteps_out, const int *__restrict__ clamp_gene,
+                                                      int clamp_width)
 {
     static_assert(!CLAMP || CALLS, "a clamped gene belongs to a call");
     constexpr int HT = 3, F2 = 2 * HT;
@@ -57,7 +59,8 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
     const bool shared = cfg.control == PHX_CTRL_SHARED;
     auto rowof = [&](int lb) -> int { return CALLS ? (lb < d.Bcall ? grp * d.Bcall + lb : B) : grp * Bt + lb; };
     const int trow_sh = CALLS ? grp : 0;
-    const int cgene = CLAMP ? __builtin_amdgcn_readfirstlane(clamp_gene[grp]) : -1;   // the call's frozen gene
+    ClampSet cset{};   // the call's held genes
+    if constexpr (CLAMP) cset = clamp_set(clamp_gene, grp, clamp_width);
     auto pair_live = [](int k) -> bool { return !(HALF && (k >> 1) % HT == HT - 1 && (k & 1)); };
     auto hc_of = [&](int c) -> int { return min(d.Hc, d.H - c * d.Hc); };
     const int cstride = d.res ? d.NB * BLKF : 0;   // floats between the chunk slots of the LDS images (0: one slot)
@@ -557,7 +560,7 @@ __global__ __launch_bounds__(256) void k1_solve_fwd3c(Net net, D1 d, W1 w, Solve
                     if constexpr (CLAMP) {
 #pragma unroll
                         for (int j = 0; j < GW; ++j)
-                            if ((blk0 + bl) * 32 + gmap(lq, goff + j) == cgene) rr[j] = 0.f;
+                            if (clamp_holds(cset, (blk0 + bl) * 32 + gmap(lq, goff + j))) rr[j] = 0.f;
                     }
                     // ---- 1. everything that needs the tiles
                     float ysI[GW], ysN[GW], y0c[GW], k0c[GW], ey[GW];

@@ -15,6 +15,28 @@ struct I3 { static constexpr int value = V; };
 // exactly twice per wave, like the natural order did.  HALF (template flag of the kernels) = the last tile is such a tile.
 __host__ __device__ constexpr int rho16(int q, int r) { return 8 * (r >> 1) + 2 * (r & 1) + 4 * (q & 1) + (q >> 1); }
 
+// The held genes of one call (the CLAMP forms of k1_solve_fwd3 / k1_solve_fwd3c): row `grp` of the [calls, width] list,
+// read once per workgroup into wave-uniform values.  Slots beyond the width are -1, which like every index that no gene
+// has (padding of a shorter set) matches nothing.
+struct ClampSet {
+    int g[PHX_CLAMP_MAX];
+};
+__device__ __forceinline__ ClampSet clamp_set(const int *__restrict__ list, int grp, int width)
+{
+    ClampSet s;
+#pragma unroll
+    for (int i = 0; i < PHX_CLAMP_MAX; ++i)
+        s.g[i] = i < width ? __builtin_amdgcn_readfirstlane(list[(long long)grp * width + i]) : -1;
+    return s;
+}
+__device__ __forceinline__ bool clamp_holds(const ClampSet &s, int gene)
+{
+    bool hit = false;
+#pragma unroll
+    for (int i = 0; i < PHX_CLAMP_MAX; ++i) hit |= gene == s.g[i];
+    return hit;
+}
+
 // Two sets of exchange buffers per workspace, used alternately (no fill between launches).  The exchange protocol needs
 // every granule of a launch to start with a tag that is not one of the launch's own (tags restart at 1).  Instead of a
 // 12-24 MB fill in front of every launch, a launch works in set S = parity of its batch group (a header word in the

@@ -515,6 +515,7 @@ def solve_forward(p, y0, t64, method, control, rtol, atol, t_per_sample, t_is_f3
 
 
 OP_CLAMPED = 11      # workspace-size key of solve_forward_clamped (phx_odeint_clamped_workspace_bytes sizes it)
+CLAMP_MAX = 4        # PHX_CLAMP_MAX: the genes one call can hold
 
 
 def clamped_plan_exists(N, H, B, T, calls):
@@ -529,11 +530,16 @@ def clamped_plan_exists(N, H, B, T, calls):
 
 def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps=0, stats=None):
     """`solve_forward` for dopri5 under shared control with calls = len(clamp) and one grid per call (t64 [calls, T]),
-    where call k holds gene clamp[k] at its initial value (phx_odeint_clamped; an int32 device tensor, -1: none).
-    ValueError where no third-generation kernel plans the calls -- solve them one by one on parameters whose g[gene]
-    is zeroed."""
+    where call k holds gene clamp[k] at its initial value, or -- clamp [calls, width <= CLAMP_MAX] -- every gene of row k
+    (phx_odeint_clamped_sets; an int32 device tensor, -1: none / padding).
+    ValueError where no third-generation kernel plans the calls -- solve them one by one on parameters whose g is
+    zeroed on the set."""
     B, N = y0.shape
-    calls = clamp.numel()
+    if clamp.dim() not in (1, 2) or (clamp.dim() == 2 and not 1 <= clamp.shape[1] <= CLAMP_MAX):
+        raise ValueError("solve_forward_clamped: clamp must be [calls] or [calls, 1 .. %d], got %s"
+                         % (CLAMP_MAX, tuple(clamp.shape)))
+    calls = clamp.shape[0]
+    width = clamp.shape[1] if clamp.dim() == 2 else 1
     if clamp.dtype != torch.int32 or clamp.device != y0.device or not clamp.is_contiguous():
         raise ValueError("solve_forward_clamped: clamp must be a contiguous int32 tensor on y0's device")
     if calls < 1 or B % calls or t64.dim() != 2 or t64.shape[0] != calls:
@@ -557,8 +563,9 @@ def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps
 
     def call(keep):
         o = _opts("dopri5", _lib.CTRL_SHARED, rtol, atol, 1, t_is_f32, max_num_steps, calls, keep)
-        return _lib.load().phx_odeint_clamped(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(clamp), _p(sol),
-                                              _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
+        return _lib.load().phx_odeint_clamped_sets(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(clamp), width,
+                                                   _p(sol), _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb,
+                                                   _stream_ptr())
 
     _solve_call(_lib.OP_ODEINT, pkey, y0.device, call)
     return sol, stats[0], stats[1], stats[2]
@@ -717,6 +724,56 @@ def knockout_effects(base, sol, genes, want_matrices=False, scores=None, shift=N
     _check_call(_lib.load().phx_knockout_effects(_p(base), _p(sol), T, K, B, N, (C.c_int * K)(*genes), _p(scores), _p(shift),
                                                  _p(magnitude), _p(ws), nbytes, _stream_ptr()))
     return scores, shift, magnitude
+
+
+OP_EPISTASIS = 13    # workspace-cache key of knockout_epistasis (phx_knockout_epistasis_workspace_bytes sizes it)
+
+
+def knockout_epistasis(base, singles, sol, ia, ib, genes, want_matrices=False, out=None):
+    """phx_knockout_epistasis: base [T, B, N] (the unperturbed solve), singles [T, G*B, N] (G single-gene calls, `genes[g]`
+    the held gene of single g), sol [T, K*B, N] (K pair calls, pair k holding the genes of singles ia[k] and ib[k]) ->
+    (scores [K], interaction_scores [K], shift, magnitude, interaction, interaction_magnitude), the four matrices [K, N] or
+    None, all on the device.  `out`: six contiguous float32 device tensors (or None) to write into instead of fresh ones
+    (a row range of a screen's result), in that order; passing a matrix implies that matrix."""
+    _require_gpu(base, "base")
+    _require_gpu(singles, "singles")
+    _require_gpu(sol, "sol")
+    ia, ib, genes = [int(i) for i in ia], [int(i) for i in ib], [int(g) for g in genes]
+    K, G = len(ia), len(genes)
+    if len(ib) != K:
+        raise ValueError("knockout_epistasis: %d first and %d second indices" % (K, len(ib)))
+    if base.dim() != 3 or not base.is_contiguous() or base.dtype != torch.float32:
+        raise ValueError("knockout_epistasis: base must be a contiguous float32 [T, B, N] block, got %s" % (tuple(base.shape),))
+    T, B, N = base.shape
+    for name, x, calls in (("singles", singles, G), ("sol", sol, K)):
+        if (x.dim() != 3 or not x.is_contiguous() or x.dtype != torch.float32 or x.device != base.device or
+                tuple(x.shape) != (T, calls * B, N)):
+            raise ValueError("knockout_epistasis: %s must be a contiguous float32 %s block on base's device, got %s"
+                             % (name, (T, calls * B, N), tuple(x.shape)))
+    out = list(out) if out is not None else [None] * 6
+    if len(out) != 6:
+        raise ValueError("knockout_epistasis: `out` names six tensors (or None)")
+    names = ("scores", "interaction_scores", "shift", "magnitude", "interaction", "interaction_magnitude")
+    for i in range(6):
+        numel = K if i < 2 else K * N
+        if out[i] is None and (i < 2 or want_matrices):
+            out[i] = torch.empty(K if i < 2 else (K, N), dtype=torch.float32, device=sol.device)
+        x = out[i]
+        if x is not None:
+            _require_gpu(x, names[i])
+            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device or x.dtype != torch.float32:
+                raise ValueError("knockout_epistasis: `%s` must be a contiguous float32 tensor of %d elements on sol's device"
+                                 % (names[i], numel))
+    key = (OP_EPISTASIS, T, K, G, B, N)
+    nbytes = _ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = _ws_bytes[key] = _lib.load().phx_knockout_epistasis_workspace_bytes(T, K, G, B, N)
+    ws = _analysis_workspace(OP_EPISTASIS, nbytes, sol.device)
+    _check_call(_lib.load().phx_knockout_epistasis(_p(base), _p(singles), _p(sol), T, K, G, B, N, (C.c_int * K)(*ia),
+                                                   (C.c_int * K)(*ib), (C.c_int * G)(*genes), _p(out[0]), _p(out[1]),
+                                                   _p(out[2]), _p(out[3]), _p(out[4]), _p(out[5]), _p(ws), nbytes,
+                                                   _stream_ptr()))
+    return tuple(out)
 
 
 OP_EFFECTS = 6       # workspace-cache key of effects_matrix (phx_effects_workspace_bytes sizes it)

@@ -239,33 +239,47 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
     return (out, nfe, nsteps) if return_stats else out
 
 
+_INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
 def _clamp_list(clamp, K, N):
-    """`clamp` of odeint_calls as K Python ints in [-1, N), checked on the host before anything is launched"""
+    """`clamp` of odeint_calls as K sorted tuples of distinct genes in [0, N) -- the set each call holds, () for none --
+    checked on the host before anything is launched.  Per call an int (-1: none) or a sequence of at most
+    engine.CLAMP_MAX ints, or for all calls a 1-D / 2-D integer tensor, -1 entries being padding."""
     if torch.is_tensor(clamp):
-        if clamp.dim() != 1 or clamp.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-            raise TypeError("odeint_calls: clamp must be a 1-D integer tensor or a sequence of ints, got %s %s"
-                            % (clamp.dtype, tuple(clamp.shape)))
+        if clamp.dim() not in (1, 2) or clamp.dtype not in _INT_DTYPES:
+            raise TypeError("odeint_calls: clamp must be a 1-D or 2-D integer tensor or a sequence of ints / int sequences, "
+                            "got %s %s" % (clamp.dtype, tuple(clamp.shape)))
         clamp = clamp.tolist()
     try:
         clamp = list(clamp)
     except TypeError:
-        raise TypeError("odeint_calls: clamp must be a sequence of %d ints" % K) from None
-    for g in clamp:
-        if isinstance(g, bool) or not hasattr(g, "__index__"):
-            raise TypeError("odeint_calls: clamp entries must be integers, got %r" % (g,))
-    clamp = [int(g) for g in clamp]
-    if len(clamp) != K:
-        raise ValueError("odeint_calls: clamp names %d genes for %d calls" % (len(clamp), K))
-    for g in clamp:
-        if g < -1 or g >= N:
-            raise ValueError("odeint_calls: clamp entry %d is not a gene of 0 .. %d (or -1: none)" % (g, N - 1))
-    return clamp
+        raise TypeError("odeint_calls: clamp must be a sequence of %d ints or int sequences" % K) from None
+    sets = []
+    for entry in clamp:
+        if hasattr(entry, "tolist"):      # numpy and tensor scalars / rows
+            entry = entry.tolist()
+        genes = list(entry) if isinstance(entry, (list, tuple, range, set, frozenset)) else [entry]
+        for g in genes:
+            if isinstance(g, bool) or not hasattr(g, "__index__"):
+                raise TypeError("odeint_calls: clamp entries must be integers, got %r" % (g,))
+        sets.append([int(g) for g in genes])
+    if len(sets) != K:
+        raise ValueError("odeint_calls: clamp names genes for %d calls, there are %d" % (len(sets), K))
+    for genes in sets:
+        for g in genes:
+            if g < -1 or g >= N:
+                raise ValueError("odeint_calls: clamp entry %d is not a gene of 0 .. %d (or -1: none)" % (g, N - 1))
+        if len(genes) > engine.CLAMP_MAX:
+            raise ValueError("odeint_calls: a clamp set of %d entries, a call holds at most %d genes"
+                             % (len(genes), engine.CLAMP_MAX))
+    return [tuple(sorted(set(g for g in genes if g >= 0))) for genes in sets]     # duplicates count once
 
 
 def _clamped_block(func, y0s, t, rtol, atol, method, options, clamp):
-    """`_calls_block` with call k's gene clamp[k] held at its initial value (-1: none): one launch of
-    phx_odeint_clamped where dopri5 plans the calls on the third-generation kernels, else the K calls one by one on a
-    parameter set whose g[gene] is zeroed -- the model the clamped call is defined by."""
+    """`_calls_block` with call k's genes clamp[k] (one gene or a set of up to four; -1: none) held at their initial
+    values: one launch of phx_odeint_clamped_sets where dopri5 plans the calls on the third-generation kernels, else the
+    K calls one by one on a parameter set whose g is zeroed on the set -- the model the clamped call is defined by."""
     K = y0s.shape[0]
     clamp = _clamp_list(clamp, K, params_of(func)[0].shape[1])      # first: a bad list is refused whatever else holds
     grids = torch.is_tensor(t) and t.ndimension() == 2
@@ -283,7 +297,8 @@ def _clamped_block(func, y0s, t, rtol, atol, method, options, clamp):
     engine.check_pending_status()
     if method == "dopri5" and engine.clamped_plan_exists(N, params[0].shape[0], B, T, K):
         p = engine.params_cached(*params)
-        genes = torch.tensor(clamp, dtype=torch.int32).to(y0.device)
+        width = max(1, max(len(c) for c in clamp))      # the list as [K, width], shorter sets padded with -1
+        genes = torch.tensor([list(c) + [-1] * (width - len(c)) for c in clamp], dtype=torch.int32).to(y0.device)
         sol, status, _, _ = engine.solve_forward_clamped(p, y2.detach().contiguous(), tK, genes, rtol, atol, t_is_f32,
                                                          max_steps)
         engine.raise_for_status(status)
@@ -295,11 +310,11 @@ def _clamped_block(func, y0s, t, rtol, atol, method, options, clamp):
     block = torch.empty((T, K, Bc, N), dtype=torch.float32, device=y0.device)
     with torch.no_grad():
         for k in range(K):
-            if clamp[k] < 0:
+            if not clamp[k]:
                 p = engine.params_cached(*params)
             else:
                 gk = g.detach().clone()
-                gk.reshape(-1)[clamp[k]] = 0.0
+                gk.reshape(-1)[list(clamp[k])] = 0.0
                 p = engine.Params(ws, bs, wp, bp, wa, gk)
             one, status, _, _ = engine.solve_forward(p, y2[k * Bc:(k + 1) * Bc], tK[k], method, control, rtol, atol, False,
                                                      t_is_f32, max_steps, step_size=options.get("step_size", 0.0))
@@ -366,10 +381,13 @@ def odeint_calls(func, y0s, t, rtol=1e-7, atol=1e-9, method=None, options=None, 
     exist (shapes served by the VALU engine).
     clamp (K ints, a sequence or an integer tensor; -1: none): call k holds gene clamp[k] at its initial value for the
     whole time course, d y[:, clamp[k]] / dt = 0 -- level 0 is a knockout, a high level an over-expression.  Exactly the
-    solve of the model whose gene_multipliers[clamp[k]] is 0 (odenet.py:85-91).  dopri5 calls that the third-generation
-    kernels plan run in one launch (phx_odeint_clamped); every other case (a fixed-grid method, step_size, the VALU
-    engine, calls of more rows than those kernels plan) runs the K calls one by one on a cloned multiplier vector with
-    that entry zeroed; the module is never modified.  The list is range-checked on the host before any launch."""
+    solve of the model whose gene_multipliers[clamp[k]] is 0 (odenet.py:85-91).  An entry may also be a sequence of 1-4
+    ints, and clamp a 2-D integer tensor [K, W <= 4] padded with -1: call k then holds every gene of its set (a
+    combination knockout; widths may differ between calls, a gene named twice counts once, the empty set holds none).
+    dopri5 calls that the third-generation kernels plan run in one launch (phx_odeint_clamped_sets); every other case
+    (a fixed-grid method, step_size, the VALU engine, calls of more rows than those kernels plan) runs the K calls one by
+    one on a cloned multiplier vector with those entries zeroed; the module is never modified.  The list is type- and
+    range-checked on the host before any launch."""
     K = y0s.shape[0]
     sol = _calls_block(func, y0s, t, rtol, atol, method, options, clamp=clamp)
     return sol.reshape((sol.shape[0], K) + tuple(y0s.shape[1:])).transpose(0, 1)
