@@ -111,25 +111,28 @@ def _fused_scan(odenet, dim, method, n, time_pts_to_project, device, genes, draw
 KnockoutEffects = collections.namedtuple("KnockoutEffects", ("genes", "scores", "shift", "magnitude"))
 
 
+def _screen_setup(name, odenet, y0, time_pts_to_project, N, host_check=None):
+    """What a knockout screen does between its argument checks and its first solve: the y0 check, host_check(T, B) -- the
+    caller's ValueErrors that need the grid -- and only then the GPU requirement on the model and y0
+    -> (y0 [B, 1, N] detached, the time grid on y0's device; default the scan's float64 arange(0, 1, 0.1))"""
+    if y0.shape[-1] != N or y0.dim() not in (2, 3) or y0.dtype != torch.float32:
+        raise ValueError("%s: y0 must be float32 [B, 1, %d] or [B, %d], got %s %s" % (name, N, N, y0.dtype, tuple(y0.shape)))
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))
+    if host_check is not None:
+        host_check(int(time_pts_to_project.shape[-1]), y0.numel() // N)
+    engine._require_gpu(params_of(odenet)[0], "odenet")
+    engine._require_gpu(y0, "y0")
+    return y0.detach().reshape(-1, 1, N), time_pts_to_project.to(y0.device)
+
+
 def _knockout_args(N, genes, value, genes_per_launch):
     """(genes, values) of `knockout_effects` as lists of G ints / floats, checked on the host before any launch"""
-    genes = list(range(N)) if genes is None else list(genes.tolist() if hasattr(genes, "tolist") else genes)
-    for g in genes:
-        if isinstance(g, bool) or not hasattr(g, "__index__"):
-            raise TypeError("knockout_effects: genes must be integers, got %r" % (g,))
-    genes = [int(g) for g in genes]
-    for g in genes:
-        if g < 0 or g >= N:
-            raise ValueError("knockout_effects: gene %d is not one of 0 .. %d" % (g, N - 1))
+    genes = list(range(N)) if genes is None else engine.int_list("knockout_effects", genes)
+    engine.check_genes("knockout_effects", genes, N)
     if not genes:
         raise ValueError("knockout_effects: no gene to clamp")
-    values = value.tolist() if hasattr(value, "tolist") else value
-    if isinstance(values, (list, tuple)):
-        if len(values) != len(genes):
-            raise ValueError("knockout_effects: %d values for %d genes" % (len(values), len(genes)))
-        values = [float(v) for v in values]
-    else:
-        values = [float(values)] * len(genes)
+    values = engine.gene_values("knockout_effects", value, len(genes))
     if not hasattr(genes_per_launch, "__index__") or int(genes_per_launch) < 1:
         raise ValueError("knockout_effects: genes_per_launch must be a positive integer")
     return genes, values
@@ -152,16 +155,8 @@ def knockout_effects(odenet, y0, genes=None, value=0.0, time_pts_to_project=None
     `pathway_permutation_test` as it is."""
     N = params_of(odenet)[0].shape[1]
     genes, values = _knockout_args(N, genes, value, genes_per_launch)      # first: refused whatever else holds
-    if y0.shape[-1] != N or y0.dim() not in (2, 3) or y0.dtype != torch.float32:
-        raise ValueError("knockout_effects: y0 must be float32 [B, 1, %d] or [B, %d], got %s %s"
-                         % (N, N, y0.dtype, tuple(y0.shape)))
-    engine._require_gpu(params_of(odenet)[0], "odenet")
-    engine._require_gpu(y0, "y0")
+    y0, t = _screen_setup("knockout_effects", odenet, y0, time_pts_to_project, N)
     device = y0.device
-    if time_pts_to_project is None:
-        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # the scan's float64 grid
-    t = time_pts_to_project.to(device)
-    y0 = y0.detach().reshape(-1, 1, N)
     B, G = y0.shape[0], len(genes)
     k_max = max(1, min(int(genes_per_launch), G))
     scores = torch.empty(G, dtype=torch.float32, device=device)
@@ -187,14 +182,6 @@ KnockoutPairs = collections.namedtuple("KnockoutPairs", ("pairs", "genes", "scor
                                                         "interaction", "interaction_magnitude", "singles"))
 
 
-def _int_list(xs, what):
-    xs = list(xs.tolist() if hasattr(xs, "tolist") else xs)
-    for g in xs:
-        if isinstance(g, bool) or not hasattr(g, "__index__"):
-            raise TypeError("knockout_pairs: %s must be integers, got %r" % (what, g))
-    return [int(g) for g in xs]
-
-
 def _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch):
     """(genes [G], values [G], pairs [K] of (a, b) genes, ia [K], ib [K] indices into genes) of `knockout_pairs`, checked
     on the host before any launch"""
@@ -202,7 +189,8 @@ def _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch):
         raise ValueError("knockout_pairs: give `genes` (all their pairs) or `pairs`; all pairs of all %d genes are never "
                          "implied" % N)
     if pairs is not None:
-        pairs = [tuple(_int_list(p, "the genes of a pair")) for p in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
+        pairs = [tuple(engine.int_list("knockout_pairs", p, "the genes of a pair"))
+                 for p in (pairs.tolist() if hasattr(pairs, "tolist") else pairs)]
         seen = set()
         for p in pairs:
             if len(p) != 2:
@@ -217,27 +205,19 @@ def _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch):
     if genes is None:
         genes = sorted(set(g for p in pairs for g in p))
     else:
-        genes = _int_list(genes, "genes")
+        genes = engine.int_list("knockout_pairs", genes)
         if len(set(genes)) != len(genes):
             raise ValueError("knockout_pairs: a gene is listed twice in `genes`")
         if len(genes) < 2:
             raise ValueError("knockout_pairs: a pair needs two genes, `genes` names %d" % len(genes))
-    for g in genes + [g for p in (pairs or []) for g in p]:
-        if g < 0 or g >= N:
-            raise ValueError("knockout_pairs: gene %d is not one of 0 .. %d" % (g, N - 1))
+    engine.check_genes("knockout_pairs", genes + [g for p in (pairs or []) for g in p], N)
     index = {g: i for i, g in enumerate(genes)}
     if pairs is None:
         pairs = [(genes[i], genes[j]) for i in range(len(genes)) for j in range(i + 1, len(genes))]
     for p in pairs:
         if p[0] not in index or p[1] not in index:
             raise ValueError("knockout_pairs: the pair (%d, %d) names a gene that `genes` does not" % p)
-    values = value.tolist() if hasattr(value, "tolist") else value
-    if isinstance(values, (list, tuple)):
-        if len(values) != len(genes):
-            raise ValueError("knockout_pairs: %d values for %d genes" % (len(values), len(genes)))
-        values = [float(v) for v in values]
-    else:
-        values = [float(values)] * len(genes)
+    values = engine.gene_values("knockout_pairs", value, len(genes))
     if isinstance(pairs_per_launch, bool) or not hasattr(pairs_per_launch, "__index__") or int(pairs_per_launch) < 1:
         raise ValueError("knockout_pairs: pairs_per_launch must be a positive integer")
     return genes, values, pairs, [index[p[0]] for p in pairs], [index[p[1]] for p in pairs]
@@ -264,21 +244,15 @@ def knockout_pairs(odenet, y0, genes=None, pairs=None, value=0.0, time_pts_to_pr
     sits at the solver's tolerance."""
     N = params_of(odenet)[0].shape[1]
     genes, values, pairs, ia, ib = _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch)   # first, whatever else holds
-    if y0.shape[-1] != N or y0.dim() not in (2, 3) or y0.dtype != torch.float32:
-        raise ValueError("knockout_pairs: y0 must be float32 [B, 1, %d] or [B, %d], got %s %s"
-                         % (N, N, y0.dtype, tuple(y0.shape)))
-    if time_pts_to_project is None:
-        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))              # the scan's float64 grid
-    G, K, T = len(genes), len(pairs), int(time_pts_to_project.shape[-1])
-    B = y0.numel() // N
-    if 4 * T * G * B * N > max_singles_bytes:
-        raise ValueError("knockout_pairs: the block of the %d single-gene solves takes 4 T G B N = %d bytes, more than "
-                         "max_singles_bytes = %d; screen fewer genes at a time" % (G, 4 * T * G * B * N, max_singles_bytes))
-    engine._require_gpu(params_of(odenet)[0], "odenet")
-    engine._require_gpu(y0, "y0")
-    device = y0.device
-    t = time_pts_to_project.to(device)
-    y0 = y0.detach().reshape(-1, 1, N)
+    G, K = len(genes), len(pairs)
+
+    def singles_fit(T, B):
+        if 4 * T * G * B * N > max_singles_bytes:
+            raise ValueError("knockout_pairs: the block of the %d single-gene solves takes 4 T G B N = %d bytes, more than "
+                             "max_singles_bytes = %d; screen fewer genes at a time" % (G, 4 * T * G * B * N, max_singles_bytes))
+
+    y0, t = _screen_setup("knockout_pairs", odenet, y0, time_pts_to_project, N, singles_fit)
+    device, B = y0.device, y0.shape[0]
     k_max = max(1, min(int(pairs_per_launch), K))
     out = [torch.empty(K, dtype=torch.float32, device=device) for _ in range(2)]
     out += [torch.empty((K, N), dtype=torch.float32, device=device) if want_matrices else None for _ in range(4)]

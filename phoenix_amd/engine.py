@@ -76,40 +76,46 @@ def forget_workspaces():
     _ws_last.clear()
 
 
-def _workspace(op, N, H, B, T, device, calls=1, grids_method=None):
-    # the size query re-plans the launch on the host: remembered per shape (and per diagnostic switch setting)
-    # grids_method: the calls have a time grid each (phx_odeint_calls_grids_workspace_bytes depends on the method)
-    key = (op, N, H, B, T, calls, grids_method) + _plan_env()
+def _ws_size(key, query, *args):
+    """the library's workspace-size function `query` of `args`, remembered under `key`: a size query re-plans the launch on
+    the host (the keys of the solves carry the plan switches, `_plan_env`)"""
     nbytes = _ws_bytes.get(key)
     if nbytes is None:
-        if calls > 1:
-            if grids_method is not None:
-                nbytes = _lib.load().phx_odeint_calls_grids_workspace_bytes(N, H, B, T, calls, _lib.METHODS[grids_method])
-            else:
-                nbytes = _lib.load().phx_odeint_calls_workspace_bytes(N, H, B, T, calls)
-            if nbytes == 0:
-                raise ValueError("a batch of %d calls x %d trajectories cannot be planned for N=%d, H=%d" %
-                                 (calls, B // calls, N, H))
-        else:
-            nbytes = _lib.load().phx_workspace_bytes(op, N, H, B, T)
-        _ws_bytes[key] = nbytes
+        nbytes = _ws_bytes[key] = getattr(_lib.load(), query)(*args)
+    return nbytes
+
+
+def _stream_buffer(op, nbytes, device, grow=1, slack=1024, solve=False):
+    """the cached uint8 buffer of `op` on the current stream of `device`, at least `nbytes` long; a new one gets
+    nbytes * grow + slack.  solve: the buffer is a solve workspace, and a new one is in no vouched-for state (`_ws_last`)"""
     key = (device.index, _stream_raw(device.index), op)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-        _ws_last.pop(key, None)
-    return buf, nbytes
+        buf = _ws_cache[key] = torch.empty(int(nbytes * grow) + slack, dtype=torch.uint8, device=device)
+        if solve:
+            _ws_last.pop(key, None)
+    return buf
+
+
+def _workspace(op, N, H, B, T, device, calls=1, grids_method=None):
+    # grids_method: the calls have a time grid each (phx_odeint_calls_grids_workspace_bytes depends on the method)
+    key = (op, N, H, B, T, calls, grids_method) + _plan_env()
+    if calls == 1:
+        nbytes = _ws_size(key, "phx_workspace_bytes", op, N, H, B, T)
+    elif grids_method is not None:
+        nbytes = _ws_size(key, "phx_odeint_calls_grids_workspace_bytes", N, H, B, T, calls, _lib.METHODS[grids_method])
+    else:
+        nbytes = _ws_size(key, "phx_odeint_calls_workspace_bytes", N, H, B, T, calls)
+    if calls > 1 and nbytes == 0:
+        raise ValueError("a batch of %d calls x %d trajectories cannot be planned for N=%d, H=%d" %
+                         (calls, B // calls, N, H))
+    return _stream_buffer(op, nbytes, device, grow=1.25, solve=True), nbytes
 
 
 def _analysis_workspace(op, nbytes, device):
     """the cached uint8 workspace of the analysis op `op` on the current stream of `device`, at least `nbytes` long (the
     callers that read counters from it view it as int32)"""
-    key = (device.index, _stream_raw(device.index), op)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=device)
-    return ws
+    return _stream_buffer(op, nbytes, device)
 
 
 def _p(t):
@@ -521,11 +527,7 @@ CLAMP_MAX = 4        # PHX_CLAMP_MAX: the genes one call can hold
 def clamped_plan_exists(N, H, B, T, calls):
     """whether phx_odeint_clamped serves `calls` dopri5 calls of B // calls rows (k1_solve_fwd3 / k1_solve_fwd3c plan
     them); the size is remembered per shape and plan-switch setting"""
-    key = (OP_CLAMPED, N, H, B, T, calls) + _plan_env()
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _ws_bytes[key] = _lib.load().phx_odeint_clamped_workspace_bytes(N, H, B, T, calls)
-    return nbytes
+    return _ws_size((OP_CLAMPED, N, H, B, T, calls) + _plan_env(), "phx_odeint_clamped_workspace_bytes", N, H, B, T, calls)
 
 
 def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps=0, stats=None):
@@ -554,11 +556,7 @@ def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps
         stats = torch.empty((3, B), dtype=torch.int32, device=y0.device)
     p.on_current_stream()
     # the solve workspace of the stream, shared with solve_forward (one launch at a time uses it)
-    key = (y0.device.index, _stream_raw(y0.device.index), _lib.OP_ODEINT)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nb:
-        ws = _ws_cache[key] = torch.empty(int(nb * 1.25) + 1024, dtype=torch.uint8, device=y0.device)
-        _ws_last.pop(key, None)
+    ws = _stream_buffer(_lib.OP_ODEINT, nb, y0.device, grow=1.25, solve=True)
     pkey = ("clamped", p.N, p.H, B, T, calls) + _plan_env()
 
     def call(keep):
@@ -603,18 +601,8 @@ OP_BACKPROP = 4      # workspace-cache key of solve_backprop (phx_odeint_backpro
 
 
 def _workspace_backprop(N, H, B, T, K, device):
-    key = (OP_BACKPROP, N, H, B, T, K) + _plan_env()
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _lib.load().phx_odeint_backprop_workspace_bytes(N, H, B, T, K)
-        _ws_bytes[key] = nbytes
-    key = (device.index, _stream_raw(device.index), OP_BACKPROP)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=device)
-        _ws_cache[key] = buf
-        _ws_last.pop(key, None)
-    return buf, nbytes
+    nbytes = _ws_size((OP_BACKPROP, N, H, B, T, K) + _plan_env(), "phx_odeint_backprop_workspace_bytes", N, H, B, T, K)
+    return _stream_buffer(OP_BACKPROP, nbytes, device, solve=True), nbytes
 
 
 def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_f32, want_grads=True, max_num_steps=0,
@@ -648,6 +636,38 @@ def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_
 OP_INFLUENCE = 5     # workspace-cache key of influence_scores (phx_influence_workspace_bytes sizes it)
 
 
+def _score_block(name, what, x, T, calls, B, N, device, layout):
+    """ValueError unless x is a contiguous float32 [T, calls*B, N] block on `device` (`layout`: how the message spells it)"""
+    if (x.dim() != 3 or not x.is_contiguous() or x.dtype != torch.float32 or x.device != device or
+            tuple(x.shape) != (T, calls * B, N)):
+        raise ValueError("%s: %s must be a contiguous float32 %s block on base's device, got %s"
+                         % (name, what, layout, tuple(x.shape)))
+
+
+def _score_base(name, base):
+    """(T, B, N) of the unperturbed solve's block, checked"""
+    if base.dim() != 3 or not base.is_contiguous() or base.dtype != torch.float32:
+        raise ValueError("%s: base must be a contiguous float32 [T, B, N] block, got %s" % (name, tuple(base.shape),))
+    return tuple(base.shape)
+
+
+def _score_outputs(name, outs, device, f32="float32 "):
+    """the outputs of a scoring pass, `outs` = [(name, tensor or None, shape, wanted)]: a wanted one that is missing is
+    allocated, a given one must be a contiguous float32 device tensor of the shape's size; -> the tensors (or None)"""
+    res = []
+    for what, x, shape, wanted in outs:
+        numel = int(np.prod(shape))
+        if x is None and wanted:
+            x = torch.empty(shape, dtype=torch.float32, device=device)
+        if x is not None:
+            _require_gpu(x, what)
+            if not x.is_contiguous() or x.numel() != numel or x.device != device or (f32 and x.dtype != torch.float32):
+                raise ValueError("%s: `%s` must be a contiguous %stensor of %d elements on sol's device"
+                                 % (name, what, f32, numel))
+        res.append(x)
+    return res
+
+
 def influence_scores(sol, pairs, B, genes, want_targets=False, scores=None, targets=None):
     """phx_influence_scores on the engine's output block sol [T, 2*pairs*B, N] (call 2j unperturbed, 2j+1 perturbed,
     `genes[j]` the perturbed gene of pair j) -> (scores [pairs], targets [pairs, N] or None), both on the device.
@@ -661,24 +681,11 @@ def influence_scores(sol, pairs, B, genes, want_targets=False, scores=None, targ
     genes = [int(g) for g in genes]
     if len(genes) != pairs:
         raise ValueError("influence_scores: %d genes for %d pairs" % (len(genes), pairs))
-    if scores is None:
-        scores = torch.empty(pairs, dtype=torch.float32, device=sol.device)
-    if targets is None and want_targets:
-        targets = torch.empty((pairs, N), dtype=torch.float32, device=sol.device)
-    for name, x, numel in (("scores", scores, pairs), ("targets", targets, pairs * N)):
-        if x is not None:
-            _require_gpu(x, name)
-            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device:
-                raise ValueError("influence_scores: `%s` must be a contiguous tensor of %d elements on sol's device"
-                                 % (name, numel))
-    key = (OP_INFLUENCE, T, pairs, B, N)
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _ws_bytes[key] = _lib.load().phx_influence_workspace_bytes(T, pairs, B, N)
-    key = (sol.device.index, _stream_raw(sol.device.index), OP_INFLUENCE)
-    ws = _ws_cache.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _ws_cache[key] = torch.empty(int(nbytes) + 1024, dtype=torch.uint8, device=sol.device)
+    # (an integer output passes here as it always has: _require_gpu checks the floating-point dtypes only)
+    scores, targets = _score_outputs("influence_scores", [("scores", scores, (pairs,), True),
+                                                          ("targets", targets, (pairs, N), want_targets)], sol.device, f32="")
+    nbytes = _ws_size((OP_INFLUENCE, T, pairs, B, N), "phx_influence_workspace_bytes", T, pairs, B, N)
+    ws = _analysis_workspace(OP_INFLUENCE, nbytes, sol.device)
     _check_call(_lib.load().phx_influence_scores(_p(sol), T, pairs, B, N, (C.c_int * pairs)(*genes), _p(scores), _p(targets),
                                                  _p(ws), nbytes, _stream_ptr()))
     return scores, targets
@@ -696,30 +703,12 @@ def knockout_effects(base, sol, genes, want_matrices=False, scores=None, shift=N
     _require_gpu(sol, "sol")
     genes = [int(g) for g in genes]
     K = len(genes)
-    if base.dim() != 3 or not base.is_contiguous() or base.dtype != torch.float32:
-        raise ValueError("knockout_effects: base must be a contiguous float32 [T, B, N] block, got %s" % (tuple(base.shape),))
-    T, B, N = base.shape
-    if (sol.dim() != 3 or not sol.is_contiguous() or sol.dtype != torch.float32 or sol.device != base.device or
-            tuple(sol.shape) != (T, K * B, N)):
-        raise ValueError("knockout_effects: sol must be a contiguous float32 [T, K*B, N] = %s block on base's device, got %s"
-                         % ((T, K * B, N), tuple(sol.shape)))
-    if scores is None:
-        scores = torch.empty(K, dtype=torch.float32, device=sol.device)
-    if want_matrices:
-        if shift is None:
-            shift = torch.empty((K, N), dtype=torch.float32, device=sol.device)
-        if magnitude is None:
-            magnitude = torch.empty((K, N), dtype=torch.float32, device=sol.device)
-    for name, x, numel in (("scores", scores, K), ("shift", shift, K * N), ("magnitude", magnitude, K * N)):
-        if x is not None:
-            _require_gpu(x, name)
-            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device or x.dtype != torch.float32:
-                raise ValueError("knockout_effects: `%s` must be a contiguous float32 tensor of %d elements on sol's device"
-                                 % (name, numel))
-    key = (OP_KNOCKOUT, T, K, B, N)
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _ws_bytes[key] = _lib.load().phx_knockout_effects_workspace_bytes(T, K, B, N)
+    T, B, N = _score_base("knockout_effects", base)
+    _score_block("knockout_effects", "sol", sol, T, K, B, N, base.device, "[T, K*B, N] = %s" % ((T, K * B, N),))
+    outs = [("scores", scores, (K,), True), ("shift", shift, (K, N), want_matrices),
+            ("magnitude", magnitude, (K, N), want_matrices)]
+    scores, shift, magnitude = _score_outputs("knockout_effects", outs, sol.device)
+    nbytes = _ws_size((OP_KNOCKOUT, T, K, B, N), "phx_knockout_effects_workspace_bytes", T, K, B, N)
     ws = _analysis_workspace(OP_KNOCKOUT, nbytes, sol.device)
     _check_call(_lib.load().phx_knockout_effects(_p(base), _p(sol), T, K, B, N, (C.c_int * K)(*genes), _p(scores), _p(shift),
                                                  _p(magnitude), _p(ws), nbytes, _stream_ptr()))
@@ -742,32 +731,16 @@ def knockout_epistasis(base, singles, sol, ia, ib, genes, want_matrices=False, o
     K, G = len(ia), len(genes)
     if len(ib) != K:
         raise ValueError("knockout_epistasis: %d first and %d second indices" % (K, len(ib)))
-    if base.dim() != 3 or not base.is_contiguous() or base.dtype != torch.float32:
-        raise ValueError("knockout_epistasis: base must be a contiguous float32 [T, B, N] block, got %s" % (tuple(base.shape),))
-    T, B, N = base.shape
+    T, B, N = _score_base("knockout_epistasis", base)
     for name, x, calls in (("singles", singles, G), ("sol", sol, K)):
-        if (x.dim() != 3 or not x.is_contiguous() or x.dtype != torch.float32 or x.device != base.device or
-                tuple(x.shape) != (T, calls * B, N)):
-            raise ValueError("knockout_epistasis: %s must be a contiguous float32 %s block on base's device, got %s"
-                             % (name, (T, calls * B, N), tuple(x.shape)))
+        _score_block("knockout_epistasis", name, x, T, calls, B, N, base.device, (T, calls * B, N))
     out = list(out) if out is not None else [None] * 6
     if len(out) != 6:
         raise ValueError("knockout_epistasis: `out` names six tensors (or None)")
     names = ("scores", "interaction_scores", "shift", "magnitude", "interaction", "interaction_magnitude")
-    for i in range(6):
-        numel = K if i < 2 else K * N
-        if out[i] is None and (i < 2 or want_matrices):
-            out[i] = torch.empty(K if i < 2 else (K, N), dtype=torch.float32, device=sol.device)
-        x = out[i]
-        if x is not None:
-            _require_gpu(x, names[i])
-            if not x.is_contiguous() or x.numel() != numel or x.device != sol.device or x.dtype != torch.float32:
-                raise ValueError("knockout_epistasis: `%s` must be a contiguous float32 tensor of %d elements on sol's device"
-                                 % (names[i], numel))
-    key = (OP_EPISTASIS, T, K, G, B, N)
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _ws_bytes[key] = _lib.load().phx_knockout_epistasis_workspace_bytes(T, K, G, B, N)
+    out = _score_outputs("knockout_epistasis", [(names[i], out[i], (K,) if i < 2 else (K, N), i < 2 or want_matrices)
+                                                for i in range(6)], sol.device)
+    nbytes = _ws_size((OP_EPISTASIS, T, K, G, B, N), "phx_knockout_epistasis_workspace_bytes", T, K, G, B, N)
     ws = _analysis_workspace(OP_EPISTASIS, nbytes, sol.device)
     _check_call(_lib.load().phx_knockout_epistasis(_p(base), _p(singles), _p(sol), T, K, G, B, N, (C.c_int * K)(*ia),
                                                    (C.c_int * K)(*ib), (C.c_int * G)(*genes), _p(out[0]), _p(out[1]),
@@ -777,6 +750,32 @@ def knockout_epistasis(base, singles, sol, ia, ib, genes, want_matrices=False, o
 
 
 OP_EFFECTS = 6       # workspace-cache key of effects_matrix (phx_effects_workspace_bytes sizes it)
+
+
+def int_list(name, xs, what="genes"):
+    """`xs` (a sequence or an array) as a list of ints; TypeError on a bool or anything that is no integer"""
+    xs = list(xs.tolist() if hasattr(xs, "tolist") else xs)
+    for g in xs:
+        if isinstance(g, bool) or not hasattr(g, "__index__"):
+            raise TypeError("%s: %s must be integers, got %r" % (name, what, g))
+    return [int(g) for g in xs]
+
+
+def check_genes(name, genes, N, lowest=0):
+    """ValueError unless every gene is one of lowest .. N - 1"""
+    for g in genes:
+        if g < lowest or g >= N:
+            raise ValueError("%s: gene %d is not one of %d .. %d" % (name, g, lowest, N - 1))
+
+
+def gene_values(name, value, n):
+    """`value`, a scalar or one level per gene, as a list of n floats"""
+    values = value.tolist() if hasattr(value, "tolist") else value
+    if isinstance(values, (list, tuple)):
+        if len(values) != n:
+            raise ValueError("%s: %d values for %d genes" % (name, len(values), n))
+        return [float(v) for v in values]
+    return [float(values)] * n
 
 
 def check_rows(rows, N):
@@ -850,10 +849,7 @@ def effects_matrix(params, mode, y=None, ph=None, rows=None, out=None):
         if tuple(out.shape) != (row1 - row0, N) or not out.is_contiguous() or out.device != params.device:
             raise ValueError("effects_matrix: `out` must be a contiguous [%d, %d] tensor on the parameters' device"
                              % (row1 - row0, N))
-    key = (OP_EFFECTS, N, H, B, mode)
-    nbytes = _ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = _ws_bytes[key] = _lib.load().phx_effects_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode])
+    nbytes = _ws_size((OP_EFFECTS, N, H, B, mode), "phx_effects_workspace_bytes", N, H, B, _lib.EFFECTS_MODES[mode])
     ws = _analysis_workspace(OP_EFFECTS, nbytes, params.device) if nbytes else None
     p = params.on_current_stream()
     _check_call(_lib.load().phx_effects_matrix(C.byref(p.c), _lib.EFFECTS_MODES[mode], _p(y), _p(ph), B, row0, row1, _p(out),

@@ -293,23 +293,11 @@ OP_HILL_JACOBIAN = 11    # workspace-cache key of HillSystem.jacobian (phx_hill_
 
 def _knockout_args(name, N, genes, value, lowest):
     """(genes, values) of a knockout screen of the simulator as lists of ints in lowest .. N - 1 and finite floats"""
-    genes = list(range(N)) if genes is None else list(genes.tolist() if hasattr(genes, "tolist") else genes)
-    for g in genes:
-        if isinstance(g, bool) or not hasattr(g, "__index__"):
-            raise TypeError("%s: genes must be integers, got %r" % (name, g))
-    genes = [int(g) for g in genes]
-    for g in genes:
-        if g < lowest or g >= N:
-            raise ValueError("%s: gene %d is not one of %d .. %d" % (name, g, lowest, N - 1))
+    genes = list(range(N)) if genes is None else engine.int_list(name, genes)
+    engine.check_genes(name, genes, N, lowest)
     if not genes:
         raise ValueError("%s: no gene to hold" % name)
-    values = value.tolist() if hasattr(value, "tolist") else value
-    if isinstance(values, (list, tuple)):
-        if len(values) != len(genes):
-            raise ValueError("%s: %d values for %d genes" % (name, len(values), len(genes)))
-        values = [float(v) for v in values]
-    else:
-        values = [float(values)] * len(genes)
+    values = engine.gene_values(name, value, len(genes))
     for v in values:
         if not np.isfinite(np.float32(v)):
             raise ValueError("%s: level %r is not a finite float32" % (name, v))
@@ -515,12 +503,7 @@ class HillSystem:
         x2 = x.detach().reshape(B, N).contiguous()
         lib = _lib.load()
         nbytes = lib.phx_hill_jacobian_workspace_bytes(B, N, E, mode)
-        ws = None
-        if nbytes:
-            wkey = (x.device.index, engine._stream_raw(x.device.index), OP_HILL_JACOBIAN)
-            ws = engine._ws_cache.get(wkey)
-            if ws is None or ws.numel() < nbytes:
-                ws = engine._ws_cache[wkey] = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=x.device)
+        ws = engine._stream_buffer(OP_HILL_JACOBIAN, nbytes, x.device, slack=256) if nbytes else None
         engine._check_call(lib.phx_hill_jacobian(*self._args(), engine._p(eptr), engine._p(ereg), engine._p(x2), B, N, E, mode,
                                                  engine._p(value), engine._p(ws), nbytes, engine._stream_ptr()))
         return HillJacobian(regulator, target, value)
