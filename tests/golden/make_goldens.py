@@ -24,6 +24,9 @@ Goldens:
   G14 breast11165   the reference at FULL size on the shipped 11 165-gene test sample (7 pairs, H = 40, config_breast.cfg):
                     its own ODENet (sparse_ init), the training loop's per-sample odeint_adjoint calls, loss_data, backward
   G15 yeast3551     the same on the shipped 3 551-gene yeast sample (23 pairs, dt = 5, H = 120, config_yeast.cfg)
+  G25 dopri5_truth  (make_golden_truth.py) an fp64 tight-tolerance truth at the shapes of every dopri5 kernel family -- fwd3 /
+                    adj3 past 32 gene blocks, fwd3c / adj3c at 2 ... 6 hidden chunks -- with unit and training-scale cotangents,
+                    and the reference's own float32 errors against it at rtol * {0.85 ... 1.15}, batched and per sample
 """
 import ast
 import os

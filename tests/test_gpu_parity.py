@@ -1766,6 +1766,55 @@ def test_training_step_recorded_into_a_graph(pa, dev, N, H, B, method):
         engine.forget_workspaces()
 
 
+@pytest.mark.parametrize("N,H,B,method", [(350, 40, 17, "dopri5"), (350, 40, 64, "rk4")])
+def test_graphed_step_with_the_optimizer_outside_the_graph(pa, dev, N, H, B, method):
+    """A step function WITHOUT the update (zero_grad, solve, backward) recorded by GraphedStep, the optimizer stepped
+    eagerly between the replays: every replay must lay the parameters out again -- the warm-up runs and the capture once
+    all hit the engine's layout cache, the graph held no layout kernel, and the replays then read the live Ws / Wp / g
+    together with a stale transposed W_alpha and stale weight images.  After every round the parameters equal, bit for
+    bit, those of the same rounds run eagerly."""
+    p = rand_params(N, H, seed=N + H + B, std=0.05)
+    r = np.random.RandomState(3)
+    y0 = torch.from_numpy(r.rand(B, 1, N).astype(np.float32)).to(dev)
+    G = torch.from_numpy((r.randn(2, B, 1, N) / (B * N)).astype(np.float32)).to(dev)
+    if method == "dopri5":
+        t = torch.from_numpy(np.stack([np.array([0.0, 0.3 + 0.01 * b]) for b in range(B)]).astype(np.float32)).to(dev)
+    else:
+        t = torch.tensor([0.0, 0.5], device=dev)
+
+    def make():
+        net = make_net(pa, dev, p)
+        opt = torch.optim.SGD(net.parameters(), lr=10.0)     # cotangents of 1/(B N): gradients of 1e-4 ... 1e-3, steps of a few percent of W_alpha
+
+        def step():
+            opt.zero_grad(set_to_none=False)
+            y = y0.detach().requires_grad_(True)
+            sol = pa.odeint_adjoint(net, y, t, method=method) if method == "dopri5" else pa.odeint(net, y, t, method=method)
+            torch.autograd.backward(sol, G)
+        for q in net.parameters():
+            q.grad = torch.zeros_like(q)
+        return net, opt, step
+
+    net_e, opt_e, step_e = make()
+    rounds = []
+    for _ in range(4):
+        step_e()
+        opt_e.step()
+        rounds.append([q.detach().clone() for q in net_e.parameters()])
+    net_g, opt_g, step_g = make()
+    gs = pa.GraphedStep(step_g, warmup=2)
+    moved = 0.0
+    for k in range(4):
+        before = [q.detach().clone() for q in net_g.parameters()]
+        gs()
+        opt_g.step()
+        gs.check_status()
+        moved = max(moved, max(float((a.detach() - b).abs().max() / b.abs().max()) for a, b in zip(net_g.parameters(), before)))
+        for a, b in zip(net_g.parameters(), rounds[k]):
+            assert torch.equal(a, b), k
+    assert moved > 1e-3          # (a condition on the inputs: steps that a stale layout cannot hide behind)
+
+
 def test_zz_median_gradient_error_of_the_suite_meets_the_north_star_bar():
     """Runs last (file order): the MEDIAN engine-vs-reference error of every multi-step dopri5 gradient comparison this
     session made (oracle with the parameter block in the norm, goldens captured from torchdiffeq) is within the

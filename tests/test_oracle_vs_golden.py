@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import g25
 from conftest import load_golden, net_from, relerr, sub
 
 KEYS = ("Ws", "bs", "Wp", "bp", "Wa", "g")
@@ -100,6 +101,72 @@ def test_g12_gradients_are_as_close_to_the_truth_as_the_references_own(oracle):
             our_err.append(max([relerr(adj, s["truth64/grad_y0"])] + [relerr(grads[k], s["truth64/grad_" + k]) for k in KEYS]))
     assert np.median(our_err) <= 1.5 * np.median(ref_err), (np.median(our_err), np.median(ref_err))
     assert max(our_err) <= 2.0 * max(ref_err), (max(our_err), max(ref_err))
+
+
+# ---- golden G25: the oracle against an fp64 truth at the shapes of every dopri5 kernel family (tests/g25.py)
+_G25 = {}
+
+
+def _g25_oracle(oracle, gold, shape, mode, theta):
+    """the oracle's errors against the truth at one case, mode and norm variant (solved once per session)"""
+    key = (shape, mode, theta)
+    if key not in _G25:
+        p, y0, t, G = g25.inputs(shape, mode)
+        net = oracle.Net(*[p[k] for k in KEYS])
+        if mode == "per":
+            tb = np.tile(t[None], (shape[2], 1))
+            sol = oracle.odeint_per_sample(net, y0, tb, method="dopri5", nthreads=8)
+            adj, gr = oracle.adjoint_backward_per_sample(net, tb, sol, G.transpose(1, 0, 2).copy(), method="dopri5",
+                                                         theta_in_norm=theta, nthreads=8)
+            sol = sol.transpose(1, 0, 2)
+        else:
+            sol = oracle.odeint(net, y0, t, method="dopri5")
+            adj, gr = oracle.adjoint_backward(net, t, sol, G, method="dopri5", theta_in_norm=theta)
+        truth = g25.truth_of(gold, shape, mode)
+        _G25[key] = g25.errors(g25.stored(shape, dict(gr, y0=adj)), truth), relerr(sol[1:], truth["sol"]), gr["g"], p["g"]
+    return _G25[key]
+
+
+@pytest.fixture(scope="module")
+def gold25():
+    return g25.load()
+
+
+def test_g25_fixture(gold25):
+    """the inputs are drawn, not stored: their checksums; the truth's tolerance and how converged it is"""
+    for shape in g25.SHAPES:
+        assert np.allclose(g25.checksums(g25.inputs(shape, "shared")[0]), g25.checksums_of(gold25, shape), rtol=1e-12, atol=0)
+    assert float(gold25["truth_rtol"]) <= 1e-11
+    for shape, mode in g25.RUNS:
+        assert float(gold25[g25.name(shape, mode) + "converged"]) < 1e-8, (shape, mode)
+        assert gold25[g25.name(shape, mode) + "ref_err"].shape == (7, 8)
+
+
+@pytest.mark.parametrize("theta_in_norm", [True, False])
+@pytest.mark.parametrize("shape,mode", g25.RUNS, ids=["%dx%dx%d-%s" % (s + (m,)) for s, m in g25.RUNS])
+def test_g25_oracle_against_the_fp64_truth(oracle, gold25, shape, mode, theta_in_norm):
+    """An independent float32 implementation of the algorithm, held to the reference's own distance from the fp64 truth
+    (the bar of tests/g25.py) before any GPU time is spent -- with the parameter block in the adjoint norm, as the
+    reference has it, and without it, as the engine's controllers run: against the truth, what leaving it out costs."""
+    assert np.allclose(g25.checksums(g25.inputs(shape, mode)[0]), g25.checksums_of(gold25, shape), rtol=1e-12, atol=0)
+    e, sol_err, grad_g, g = _g25_oracle(oracle, gold25, shape, mode, theta_in_norm)
+    print(g25.table_line("theta" if theta_in_norm else "no theta", shape, mode, e, gold25))
+    assert sol_err < TOL_DOPRI
+    bar, bar_row, _ = g25.bars(gold25, shape, mode)
+    assert g25.worst(e) <= bar, (e, bar)
+    assert e["row"] <= bar_row, (e["row"], bar_row)
+    assert np.any(g <= 0) and np.all(grad_g[g <= 0] == 0.0)
+
+
+@pytest.mark.parametrize("theta_in_norm", [True, False])
+@pytest.mark.parametrize("regime", ["unit", "train"])
+def test_g25_oracle_median_of_a_regime(oracle, gold25, regime, theta_in_norm):
+    runs = [(s, m) for s, m in g25.RUNS if g25.regime(s) == regime]
+    ours = [g25.worst(_g25_oracle(oracle, gold25, s, m, theta_in_norm)[0]) for s, m in runs]
+    ref = np.concatenate([g25.bars(gold25, s, m)[2] for s, m in runs])
+    print("%s, theta %s: oracle median %.2e max %.2e | reference median %.2e max %.2e" % (
+        regime, theta_in_norm, np.median(ours), max(ours), np.median(ref), ref.max()))
+    assert np.median(ours) <= g25.MEDIAN * np.median(ref), (np.median(ours), np.median(ref))
 
 
 def test_g4_per_sample_loop(oracle):
