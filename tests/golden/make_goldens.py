@@ -27,6 +27,9 @@ Goldens:
   G25 dopri5_truth  (make_golden_truth.py) an fp64 tight-tolerance truth at the shapes of every dopri5 kernel family -- fwd3 /
                     adj3 past 32 gene blocks, fwd3c / adj3c at 2 ... 6 hidden chunks -- with unit and training-scale cotangents,
                     and the reference's own float32 errors against it at rtol * {0.85 ... 1.15}, batched and per sample
+  G26 fixed_truth   (make_golden_fixed_truth.py) the reference's odeint_adjoint with euler / midpoint / rk4 in float64, with and
+                    without options["step_size"] and with a backward step of its own: the anchor of the float64 arbiter
+                    (tests/g26.py) that the fixed-grid kernels are held to at every launch geometry
 """
 import ast
 import os
