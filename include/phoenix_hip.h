@@ -610,6 +610,12 @@ int phx_debug_calls_grids_launches(int N, int H, int B, int T, int calls, int me
 #define PHX_DEBUG_PLAN_FIELDS 37
 int phx_debug_plan(int op, int kernel_id, int cus, int N, int H, int B, int T, int control, int method, int calls,
                    long long *out);
+/* Diagnostic only, needs no device: where a k1_solve_adj3 workspace says what became of the last step's quadrature.
+ * *deferred = byte offset of one uint32 per batch group (1: the group left the visit of its last step to k3_tail_adj3 in
+ * the workspace's latest launch, 0: it ran it itself), *served = byte offset of the uint32 in which the latest tail launch
+ * left the number of deferred groups it worked on.  Returns 1 when the environment has the tail kernel on
+ * (PHX_V3_TAIL=0 switches it off), else 0. */
+int phx_debug_adj3_tail_words(size_t *deferred, size_t *served);
 
 #ifdef __cplusplus
 }

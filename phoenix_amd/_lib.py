@@ -42,7 +42,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_pathway_permutations", "phx_hill_jacobian_workspace_bytes", "phx_hill_jacobian",
            "phx_odeint_clamped_workspace_bytes", "phx_odeint_clamped", "phx_knockout_effects_workspace_bytes",
            "phx_knockout_effects", "phx_hill_knockouts", "phx_debug_hill_knockouts_kpt", "phx_odeint_clamped_sets",
-           "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis")
+           "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -132,6 +132,7 @@ def load():
     lib.phx_layout_params.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     lib.phx_debug_forward_kernel_m.argtypes = [C.c_int] * 6
     lib.phx_debug_solve_launches.argtypes = [C.c_int] * 7
+    lib.phx_debug_adj3_tail_words.argtypes = [C.POINTER(C.c_size_t)] * 2
     lib.phx_influence_workspace_bytes.argtypes = [C.c_int] * 4
     lib.phx_influence_workspace_bytes.restype = C.c_size_t
     lib.phx_influence_scores.argtypes = [vp] + [C.c_int] * 4 + [C.POINTER(C.c_int), vp, vp, vp, C.c_size_t, vp]

@@ -37,7 +37,7 @@ PROF_UNITS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_adj2.hip")
 # (the store-data hazard is checked on these listings, tools/check_store_hazard.py); phx_neighbors.hip stores plainly and
 # is listed so that the check sees that
 LISTINGS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_fwd3c.hip", "phx_adj3c.hip", "phx_bp.hip", "phx_effects.hip",
-            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip")
+            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip", "phx_adj3t.hip")
 
 
 def sources():

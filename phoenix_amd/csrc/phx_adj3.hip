@@ -83,8 +83,8 @@ const void *prepare_adj3(SolveArgs &a, const phx_params *p, hipStream_t st)
 
 hipError_t launch_adj3(const void *fn, const SolveArgs &a, hipStream_t st)
 {
-    // PHX_PROF=2: + per-block timers of the sweeps, 3: + of the quadrature
-    const int flags = a.grads | (a.w.prof_level == 2 ? 2 : 0) | (a.w.prof_level == 3 ? 4 : 0);
+    // PHX_PROF=2: + per-block timers of the sweeps, 3: + of the quadrature; 8: k3_tail_adj3 follows (reduce_adj3)
+    const int flags = a.grads | (a.w.prof_level == 2 ? 2 : 0) | (a.w.prof_level == 3 ? 4 : 0) | (adj3_tail_on(a) ? 8 : 0);
     return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.t, a.y_saved,
                              a.grad_y, a.adj_y0, a.status, a.nfe, a.nsteps, flags, a.PP);
 }
@@ -92,6 +92,9 @@ hipError_t launch_adj3(const void *fn, const SolveArgs &a, hipStream_t st)
 bool reduce_adj3(const SolveArgs &a, int npart, const phx_grads *g, int overwrite, hipStream_t st)
 {
     const D1 &d = a.d;
+    // the tail kernel: the visits the solve deferred + the sum over the groups, unconditionally (the workspace header says
+    // which groups deferred: no host-side decision, so a captured step replays it as it is)
+    if (adj3_tail_on(a)) return launch_adj3_tail(a, g, overwrite, st);
     const long long total = (long long)d.nblk * (4 * d.HT * 2 * 64) + d.N + 2 * d.H;
     hipLaunchKernelGGL((k3_reduce_grads<3>), dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, st, a.w.dtheta, npart,
                        a.PP, d.N, d.H, d.nblk, g->Ws, g->Wp, g->WaT, g->g, g->bs, g->bp, overwrite, g->Wa);

@@ -228,6 +228,11 @@ const Backend &adj3c_backend();
 // points of its own
 const Backend &bp_backend();
 
+// k3_tail_adj3 (phx_adj3t.hip), launched behind k1_solve_adj3 in place of its gradient reduce: adj3_tail_on says whether
+// this launch runs with it (the solve kernel then may defer its last visit, and the reduce step launches the tail)
+bool adj3_tail_on(const SolveArgs &a);
+bool launch_adj3_tail(const SolveArgs &a, const phx_grads *g, int overwrite, hipStream_t st);
+
 // the CALLS + CLAMP forms of k1_solve_fwd3 / k1_solve_fwd3c (phx_odeint_clamped), compiled in units of their own
 // (phx_fwd3k.hip, phx_fwd3ck.hip) so that the parallel build is no longer than before
 const void *fwd3_clamp_kernel(bool half);

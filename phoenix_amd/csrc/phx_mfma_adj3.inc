@@ -18,11 +18,16 @@
 //     parameter-gradient accumulators of the block stay in registers over the seven stages, and the dense-output /
 //     jump / new (y0, a0) of the accept pass are formed from the same registers.
 //
+//   * the visit of the step that ends the solve can leave the kernel: a group whose trajectories all reach t_0 with the
+//     first accepted step of the last interval writes their controller values into the head of its unwritten partial
+//     and k3_tail_adj3 (phx_mfma_adj3_tail.inc), launched behind this kernel in place of k3_reduce_grads, runs the visit
+//     on the whole chip (`deferred` below; DESIGN.md section 2).
+//
 // Tile passes (11.4 MB each at C4) per dopri5 step: sweeps 58 loads + 12 stores, quadrature + accept 16 + 2
 // (k1_solve_adj: about 147).
 namespace {
 
-enum { C_Y0 = 0, C_A0 = 1, C_KY = 2, C_KA = 9 };
+// (C_Y0, C_A0, C_KY, C_KA: the private vectors' slots, phx_mfma_v3common.inc -- k3_tail_adj3 reads them too)
 constexpr int NVEC_ADJ3 = 16;
 
 __host__ __device__ inline size_t ctl3_bytes(int Bt, int ntg)
@@ -33,7 +38,8 @@ __host__ __device__ inline size_t ctl3_bytes(int Bt, int ntg)
 
 // grads (+)= sum over the wave partials of k1_solve_adj3 (accumulator-native order, see the kernel), fixed order =>
 // deterministic.  One thread per (gene block, accumulator, lane): npart coalesced float4 loads, four scattered stores
-// (rows 16 f + rho16(lq, r) of one gene); the tail threads sum dg, dbs, dbp.
+// (rows 16 f + rho16(lq, r) of one gene); the tail threads sum dg, dbs, dbp.  Launched where the tail kernel is off
+// (adj3_tail_on, phx_adj3t.hip: small launches, PHX_V3_TAIL=0); k3_tail_adj3 sums and writes the same way.
 template <int HT>
 __global__ __launch_bounds__(256) void k3_reduce_grads(const float *__restrict__ dtheta, int npart, long long PP, int N, int H,
                                                        int nblk, float *gWs, float *gWp, float *gWaT, float *gg, float *gbs,
@@ -109,6 +115,9 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
 {
     const int want_grads = want_grads_flags & 1;
     const bool prof_sweep = (want_grads_flags & 2) != 0, prof_quad = (want_grads_flags & 4) != 0;   // PHX_PROF=2 / 3
+    // 8: the host launches k3_tail_adj3 behind this kernel -- a group whose trajectories all end the solve in its first
+    // accepted step leaves that step's quadrature + accept visit to it (`deferred`, in front of quad_accept below)
+    const bool may_defer = (want_grads_flags & 8) != 0;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lq = lane >> 4;
     // wave-uniform by construction: telling the compiler keeps every tile / row base address in scalar registers
@@ -1044,13 +1053,13 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
                     }
                 };
                 stage(I3<0>{}); stage(I3<1>{}); stage(I3<2>{}); stage(I3<3>{}); stage(I3<4>{}); stage(I3<5>{});
-                float gy8[8], ys8[8];
+                float gy4[4], ys4[4];
                 {   // jump data of the trajectories that reach t_{i-1} in this step (adjoint.py:152-154), requested in
-                    // front of the last stage so that its work covers them
+                    // front of the last stage so that its work covers them: the lane's four genes of this gene half
                     const long long ro = (long long)(iv - 1) * d.BN + (long long)b * N;
-                    const int g0 = gene0 + gmap(lq, 0);
-                    row_load8(grad_y, ro, g0, N, okb && fin == 1, 0.f, gy8);
-                    row_load8(y_saved, ro, g0, N, okb && fin == 1, 0.5f, ys8);
+                    const int g0 = gene0 + gmap(lq, 4 * s2);
+                    row_load4(grad_y, ro, g0, N, okb && fin == 1, 0.f, gy4);
+                    row_load4(y_saved, ro, g0, N, okb && fin == 1, 0.5f, ys4);
                 }
                 stage(I3<6>{});
                 asm volatile("; PHXMARK accept");
@@ -1071,8 +1080,8 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
                         am[j] += ka[6][j] * (dts * DP_CMID[6]);
                         if (fin == 1) {
                             const float aout = interp_eval(a0v[j], a1[j], a0v[j] + am[j], ka[0][j], ka[6][j], dts, ix);
-                            anew[j] = aout + gy8[4 * s2 + j];
-                            ynew[j] = ys8[4 * s2 + j];
+                            anew[j] = aout + gy4[j];
+                            ynew[j] = ys4[j];
                         } else {
                             anew[j] = a1[j];
                             ynew[j] = y1[j];
@@ -1136,6 +1145,7 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
         tm.mark(10);
     };
 
+    bool deferred = false;   // this group left its (only) visit to the tail kernel
     float nv[2];
     for (int iv = T - 1; iv >= 1; --iv) {
         // ---------------------------------------------------------------- dopri5 on [u0, u_end]
@@ -1267,7 +1277,36 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
             }
             __syncthreads();
             tm.mark(9);
-            quad_accept(iv);
+            // The visit of the step that ends the solve goes to the tail kernel when nothing of the group's partial is
+            // written yet and every trajectory of the group is either out already or reaches t_0 with this accepted step
+            // (the benchmark's and training's case: one step per solve).  The decision is the same in all G workgroups
+            // of the group (it reads controller values only); every other case takes the visit here, as before.
+            if (may_defer && want_grads && iv == 1 && gfirst) {
+                bool ok = !x.aborted;
+                for (int lb = tid; lb < Bt; lb += blockDim.x) ok = ok && (c.done[lb] || (c.accept[lb] && c.fin[lb] == 1));
+                ok = __all(ok) != 0;
+                if (lane == 0) c.misc[4 + wv] = ok ? 1 : 0;   // (count_active's words: free between its calls)
+                __syncthreads();
+                for (int k = 0; k < d.NW; ++k) ok = ok && c.misc[4 + k] != 0;
+                deferred = ok;
+            }
+            if (deferred) {
+                if (gt == 0) {
+                    for (int lb = tid; lb < Bt; lb += blockDim.x) {
+                        float *rec = dth + (long long)lb * TR_N;
+                        for (int j = 0; j < 7; ++j) rec[TR_W + j] = wq[lb * 8 + j];
+                        rec[TR_DT] = c.dtp[lb];
+                        rec[TR_SG] = c.sgn[lb];
+                        const InterpX ix = make_interp_x(xfin[lb]);
+                        rec[TR_X] = ix.x1; rec[TR_X + 1] = ix.x2; rec[TR_X + 2] = ix.x3; rec[TR_X + 3] = ix.x4;
+                        rec[TR_ADV] = (!c.done[lb] && c.accept[lb]) ? 1.0f : 0.f;
+                        rec[TR_ADV + 1] = 0.f; rec[TR_ADV + 2] = 0.f;
+                    }
+                    for (int i = tid; i < ntg; i += blockDim.x) reinterpret_cast<int *>(dth + (long long)Bt * TR_N)[i] = kbs[i];
+                }
+                tm.mark(10);
+            } else
+                quad_accept(iv);
             __syncthreads();
             if (tid < ntg && rotf[tid]) kbs[tid] = ring(kbs[tid], 6);
             if (tid < Bt && !c.done[tid] && c.fin[tid]) {
@@ -1278,9 +1317,10 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
         }
     }
 
-    // ---- results
+    // ---- results (a deferred group's adj_y0 comes out of the tail kernel's accept pass)
     __syncthreads();
-    for (int s = 0; s < d.TPW; ++s) {
+    if (want_grads && gt == 0 && tid == 0) xs.hdr[XH_DEFER + grp] = deferred ? 1u : 0u;
+    for (int s = 0; s < d.TPW && !deferred; ++s) {
         const int ttl = wtile + s;
         if (ttl >= ntg) continue;
         const int b = grp * Bt + ttl * 16 + li;
@@ -1292,7 +1332,7 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
     }
     // a group that never stepped (every trajectory failed before its first step) still owes its partial: every wave
     // clears the slots it would have written (quad_accept's ownership: half blocks wave, wave + NW, ...)
-    if (want_grads && gfirst) {
+    if (want_grads && gfirst && !deferred) {
         for (int hb = wv; hb < 2 * nbl; hb += d.NW) {
             const int bl = hb >> 1, s2 = hb & 1;
             float4 *pn = reinterpret_cast<float4 *>(dth) + (long long)(blk0 + bl) * (F4 * 2 * 64) + lane;

@@ -94,6 +94,18 @@ __device__ __forceinline__ void xset_end(const XSet &xs, int grp, int gt, int G)
     }
 }
 
+// Hand-over of k1_solve_adj3's last quadrature + accept visit to the tail kernel (k3_tail_adj3, phx_mfma_adj3_tail.inc).
+// A batch group that defers the visit writes, into the head of its own (otherwise unwritten) gradient partial, one record
+// of TR_N floats per trajectory -- the seven stage weights, the step, the direction, the powers of the dense-output
+// fraction, 1.0 where the trajectory advances -- and behind the Bt records the ring base of every trajectory tile; header
+// word XH_DEFER + grp of the workspace says whether the group deferred in this launch (written by every launch that
+// wants gradients: the partial itself cannot say, any bit pattern may be a gradient).  XH_SERVED: the number of deferred
+// groups the last tail launch worked on (diagnostic; phx_debug_adj3_tail_words).
+enum { C_Y0 = 0, C_A0 = 1, C_KY = 2, C_KA = 9 };   // k1_solve_adj3's private vectors: Y0, A0, KY[7], KA[7]
+enum { TR_W = 0, TR_DT = 7, TR_SG = 8, TR_X = 9, TR_ADV = 13, TR_N = 16 };
+constexpr int XH_DEFER = 768, XH_SERVED = 300;   // (header words: [0, 256) parity, 256 / 257 abort flags, [512, 768) started)
+__host__ __device__ inline size_t tail_record_floats(int Bt, int ntg) { return (size_t)Bt * TR_N + (size_t)ntg; }
+
 // Private tiles and the transposed hidden rows are addressed through buffer resources: the address of an access is
 // (resource in SGPRs) + (scalar offset of the tile, computed by the scalar unit) + (ONE 32-bit lane offset shared by all
 // accesses) + immediate.  With flat 64-bit pointers the compiler keeps a per-lane 64-bit address per live tile pointer

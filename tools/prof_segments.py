@@ -98,4 +98,24 @@ for i, n in enumerate(names):
     if us[:, i].max() > 0:
         print("  %-24s mean %8.1f us  min %8.1f  max %8.1f   (%4.1f%%)" % (n, us[:, i].mean(), us[:, i].min(), us[:, i].max(),
                                                                        100 * us[:, i].mean() / tot.mean()))
+if kern == 3:
+    # what follows k1_solve_adj3 on the stream -- k3_tail_adj3 (the deferred last visits + the sum over the groups), or
+    # k3_reduce_grads with PHX_V3_TAIL=0 -- has no timers of its own: events behind the solve kernel and behind the call
+    evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(10)]
+    for tri in evs:
+        for e in tri:
+            e.record()       # instantiates the underlying hipEvent_t
+    torch.cuda.synchronize()
+    for tri in evs:
+        lib.phx_debug_set_kernel_events(C.c_void_p(tri[0].cuda_event), C.c_void_p(tri[1].cuda_event))
+        engine.solve_adjoint(p, t64, sol, G, wl["method"], _lib.CTRL_PER_TRAJECTORY, 1e-7, 1e-9, True, True)
+        tri[2].record()
+    torch.cuda.synchronize()
+    off_d, off_s = C.c_size_t(0), C.c_size_t(0)
+    tail_on = lib.phx_debug_adj3_tail_words(C.byref(off_d), C.byref(off_s)) == 1
+    ndef = int(ws[off_d.value: off_d.value + 4 * plan[4]].cpu().numpy().view(np.uint32).sum()) if tail_on else 0
+    print("  solve kernel (events)    median %6.1f us;  behind it, %s: median %6.1f us  (%d of %d groups deferred their last visit)"
+          % (1e3 * np.median([a.elapsed_time(b) for a, b, _ in evs]),
+             "k3_tail_adj3" if ndef else "k3_reduce_grads", 1e3 * np.median([b.elapsed_time(c) for _, b, c in evs]),
+             ndef, plan[4]))
 print("nfe/traj", int(nfe[0]), "batch evals", int(nfe.sum()) / B)
