@@ -357,6 +357,27 @@ int phx_hill_knockouts(const int *code, const int *off, const int *len, const fl
                        float *out, int B, int N, void *stream);
 int phx_debug_hill_knockouts_kpt(int N);
 
+/* phx_hill_knockouts with a held SET per call (additive, ABI 7): the truth of a combination screen (phx_odeint_clamped_sets
+ * + phx_knockout_epistasis).  genes_host / values_host are HOST arrays [K, width], row-major, 1 <= width <=
+ * PHX_HILL_HOLD_MAX: call k starts from x0 with every gene of row k set to that entry's level, and the rate of each of them
+ * is 0 in every stage of every sub-step.  -1 entries pad a shorter set and their level is not looked at; a row of -1 alone
+ * is the unperturbed call.  Everything else is phx_hill_knockouts: the out [T, K * B, N] layout, the integrator, the
+ * interpreter, the calls per workgroup and genes per thread, no remainder path, strided grids.  The width of a slot's row
+ * is a template parameter of the same kernel, instantiated at 1 (phx_hill_knockouts itself), 2 and 4 -- a width of 3 runs
+ * at 4 -- and the one difference is the clamp test, "the gene is in the slot's row".  A (gene, slot) that is not held is
+ * computed without a look at the row: the bits of a call do not depend on the width it runs at, on the order of its row
+ * or on the calls beside it, so a 1-entry row equals the phx_hill_knockouts call, and a gene that one held gene of a pair
+ * cannot reach has the bits it has in the other gene's single call -- the second difference of a pair screen is exactly 0
+ * at every target that is not a common descendant of both.  The launch arguments stay at 2 KiB: 256 / 128 / 64 calls per
+ * launch at the instantiated widths 1 / 2 / 4.  Nothing allocates, copies from pageable memory or synchronises.
+ * PHX_ERR_BAD_ARG with nothing launched: everything phx_hill_knockouts refuses, width < 1 or > PHX_HILL_HOLD_MAX, an entry
+ * outside -1 .. N - 1, a level that is not finite on an entry that is not -1, a gene twice in one row (two levels would be
+ * ambiguous). */
+#define PHX_HILL_HOLD_MAX 4
+int phx_hill_knockout_sets(const int *code, const int *off, const int *len, const float *consts, const float *x0,
+                           const double *times, int T, double dt_max, const int *genes_host, const float *values_host,
+                           int width, int K, float *out, int B, int N, void *stream);
+
 /* the scoring tail of the gene-influence scan (find_gene_influences.py:64-77) on the solver's
  * own output.  sol [T, 2 * pairs * B, N] is the block phx_odeint wrote for 2 * pairs calls of B rows (opts->calls): call
  * 2j is the unperturbed solve of pair j, call 2j + 1 the perturbed one; genes_host [pairs] (HOST) names the perturbed

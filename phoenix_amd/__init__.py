@@ -9,10 +9,11 @@ from .training import get_true_val_set_r2, my_r_squared, training_step, validati
 from .graphs import GraphedStep  # noqa: F401
 from .data import DataHandler, readcsv, writecsv  # noqa: F401
 from .prior import PriorMatrix, prior_targets, read_prior_matrix  # noqa: F401
-from .analysis import (Edges, JacobianRecovery, KnockoutEffects, KnockoutPairs, KnockoutPerGene,  # noqa: F401
-                       KnockoutRecovery, KnockoutRecoveryScores, Neighbors, NetworkScore, Pathways,
+from .analysis import (Edges, EpistasisPerPair, EpistasisRecovery, EpistasisRecoveryScores,  # noqa: F401
+                       JacobianRecovery, KnockoutEffects, KnockoutPairs, KnockoutPerGene, KnockoutRecovery, KnockoutRecoveryScores, Neighbors, NetworkScore, Pathways,
                        PermutationTest, consolidate_gene_scores, effects_at, effects_edges, effects_matrix,
-                       effects_neighbors, gene_influence_matrix, gene_influence_scores, jacobian_matrix,
+                       effects_neighbors, epistasis_recovery, epistasis_recovery_scores, gene_influence_matrix,
+                       gene_influence_scores, jacobian_matrix,
                        jacobian_recovery, knockout_effects, knockout_pairs, knockout_recovery, knockout_recovery_scores,
                        network_score,
                        pathway_permutation_test, read_network, read_pathways, recovery_scores, write_link_list,

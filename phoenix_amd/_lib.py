@@ -42,7 +42,8 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_pathway_permutations", "phx_hill_jacobian_workspace_bytes", "phx_hill_jacobian",
            "phx_odeint_clamped_workspace_bytes", "phx_odeint_clamped", "phx_knockout_effects_workspace_bytes",
            "phx_knockout_effects", "phx_hill_knockouts", "phx_debug_hill_knockouts_kpt", "phx_odeint_clamped_sets",
-           "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words")
+           "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words",
+           "phx_hill_knockout_sets")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -169,6 +170,8 @@ def load():
     lib.phx_hill_knockouts.argtypes = [vp] * 6 + [C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, vp,
                                        C.c_int, C.c_int, vp]
     lib.phx_debug_hill_knockouts_kpt.argtypes = [C.c_int]
+    lib.phx_hill_knockout_sets.argtypes = [vp] * 6 + [C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int,
+                                           C.c_int, vp, C.c_int, C.c_int, vp]
     lib.phx_odeint_clamped_sets.argtypes = [C.POINTER(PhxParams), vp, vp, C.c_int, C.c_int, C.POINTER(PhxSolveOpts), vp,
                                             C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.phx_knockout_epistasis_workspace_bytes.argtypes = [C.c_int] * 5

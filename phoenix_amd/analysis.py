@@ -618,6 +618,73 @@ def knockout_recovery(odenet, system, y0, genes=None, value=0.0, time_pts_to_pro
                             _pearson(_average_ranks(a), _average_ranks(b)), true, learned)
 
 
+# ------------------------------------------------------------------ recovery of the simulator's pair screen (epistasis)
+EpistasisRecoveryScores = collections.namedtuple("EpistasisRecoveryScores", ("n_entries", "sign_agreement", "pearson", "spearman",
+                                                                             "slope", "per_pair"))
+EpistasisPerPair = collections.namedtuple("EpistasisPerPair", ("n_entries", "sign_agreement", "pearson", "spearman", "slope"))
+EpistasisRecovery = collections.namedtuple("EpistasisRecovery", ("pairs", "n_entries", "sign_agreement", "pearson", "spearman",
+                                                                 "slope", "per_pair", "joint", "scores_spearman", "true",
+                                                                 "learned"))
+
+
+def epistasis_recovery_scores(pairs, true_interaction, learned_interaction, min_effect=0.0):
+    """`recovery_scores` of two pair screens' interaction matrices ([K, N], tensors or arrays; float64 on the host), built
+    like `knockout_recovery_scores`.  Entry (k, n) counts iff n is neither gene of pairs[k] (a held gene is no prediction)
+    and |true_interaction[k, n]| > min_effect (with the default 0: the common descendants of both genes -- the simulator's
+    interaction is exactly 0 elsewhere).  Returns EpistasisRecoveryScores(n_entries, sign_agreement, pearson, spearman,
+    slope, per_pair): the four statistics pooled over the counted entries, and per_pair = EpistasisPerPair(n_entries int64
+    [K], sign_agreement, pearson, spearman, slope float64 [K]), the same over the counted entries of each pair.  A statistic
+    that is not defined is NaN: every one of a pair (or a screen) without a counted entry."""
+    t, l = _host_array(true_interaction).astype(np.float64), _host_array(learned_interaction).astype(np.float64)
+    pairs = [tuple(int(g) for g in p) for p in pairs]
+    if t.ndim != 2 or t.shape != l.shape or t.shape[0] != len(pairs):
+        raise ValueError("epistasis_recovery_scores: true_interaction and learned_interaction must both be [%d, N], got %s "
+                         "and %s" % (len(pairs), t.shape, l.shape))
+    K, N = t.shape
+    for p in pairs:
+        if len(p) != 2 or min(p) < 0 or max(p) >= N:
+            raise ValueError("epistasis_recovery_scores: %r is not a pair of genes of 0 .. %d" % (p, N - 1))
+    if not float(min_effect) >= 0:
+        raise ValueError("epistasis_recovery_scores: min_effect must be >= 0, got %r" % (min_effect,))
+    counted = np.abs(t) > float(min_effect)
+    for k, p in enumerate(pairs):
+        counted[k, list(p)] = False
+    per = np.full((K, 4), np.nan)
+    for k in range(K):
+        per[k] = recovery_scores(t[k, counted[k]], l[k, counted[k]])
+    n_each = counted.sum(axis=1).astype(np.int64)
+    return EpistasisRecoveryScores(int(n_each.sum()), *recovery_scores(t[counted], l[counted]),
+                                   EpistasisPerPair(n_each, per[:, 0].copy(), per[:, 1].copy(), per[:, 2].copy(),
+                                                    per[:, 3].copy()))
+
+
+def epistasis_recovery(odenet, system, y0, genes=None, pairs=None, value=0.0, time_pts_to_project=None, method="dopri5",
+                       dt_max=0.01, min_effect=0.0, pairs_per_launch=8):
+    """Does a model trained on in-silico data recover the LOGIC of the network -- where two knockouts together do more or
+    less than the sum of each alone?  The model's pair screen, `knockout_pairs(odenet, y0, genes, pairs, value,
+    time_pts_to_project, method, pairs_per_launch)`, is held against the truth, `system.knockout_pairs` (a `HillSystem`
+    whose targets combine their regulators through AND / OR / NOT gates: the same states, pairs, levels and time points,
+    integrated with sub-steps <= dt_max).  Returns EpistasisRecovery(pairs, n_entries, sign_agreement, pearson, spearman,
+    slope, per_pair, joint, scores_spearman, true, learned): `epistasis_recovery_scores` of the two interaction matrices,
+    pooled and per pair; joint, the same of the two shift matrices of the pairs (is the joint effect itself predicted);
+    scores_spearman, the Spearman correlation of the two interaction_scores vectors (does the model rank the interacting
+    pairs as the truth does); and the two KnockoutPairs.  `HillSystem.coregulator_pairs` names the pairs that meet in a gate.
+    ValueError before any launch when the model's gene count is not `system.N`."""
+    N = params_of(odenet)[0].shape[1]
+    if N != system.N:
+        raise ValueError("epistasis_recovery: the model has %d genes, the system %d" % (N, system.N))
+    genes, values, pairs, _, _ = _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch)
+    if time_pts_to_project is None:
+        time_pts_to_project = torch.from_numpy(np.arange(0, 1, 0.1))
+    learned = knockout_pairs(odenet, y0, genes, pairs, values, time_pts_to_project, method, pairs_per_launch)
+    true = system.knockout_pairs(y0, genes, pairs, values, time_pts_to_project, dt_max)
+    s = epistasis_recovery_scores(pairs, true.interaction, learned.interaction, min_effect)
+    joint = epistasis_recovery_scores(pairs, true.shift, learned.shift, min_effect)
+    a, b = np.asarray(true.interaction_scores, np.float64), np.asarray(learned.interaction_scores, np.float64)
+    return EpistasisRecovery(pairs, s.n_entries, s.sign_agreement, s.pearson, s.spearman, s.slope, s.per_pair, joint,
+                             _pearson(_average_ranks(a), _average_ranks(b)), true, learned)
+
+
 # ------------------------------------------------------------------ pathway permutation tests (SURVEY.md row 22)
 def consolidate_gene_scores(gene_names, scores):
     """One score per gene symbol from one score per array entry (create_permutation_test_files_aws.R:68-84).  An entry

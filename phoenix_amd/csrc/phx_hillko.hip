@@ -32,6 +32,13 @@
 //   launches      Clamped genes and levels travel as launch arguments, HK_CALLS_PER_LAUNCH calls per launch (2 KiB).
 //                 Groups are strided over a capped gridDim.x and rows over a capped gridDim.y: neither K nor B is bounded
 //                 by a grid dimension.  Nothing allocates, copies or synchronises.
+//   sets          phx_hill_knockout_sets: a call holds a SET of up to PHX_HILL_HOLD_MAX genes, each at its own level (pair
+//                 and higher-order knockouts).  The width W of a slot's row of held genes is a template parameter of the
+//                 same kernel -- W = 1 is phx_hill_knockouts, instruction for instruction -- and the only difference is
+//                 the clamp test, "gene is one of the W entries of the slot's row" (-1 pads a shorter set and matches no
+//                 gene).  W = 1, 2, 4 are instantiated, a width of 3 runs padded at W = 4.  The launch arguments stay at
+//                 2 KiB: HK_CALLS_PER_LAUNCH / W calls per launch.  The arithmetic of a (gene, slot) that is not held does
+//                 not look at W: a call's bits are the same at every width its set fits in.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -52,9 +59,12 @@ constexpr int HK_MAX_GRID_Y = 4096;        // rows are strided over gridDim.y
 constexpr int HK_SLOT_BUDGET = 8;          // KPT x GPT (see `budget` above)
 constexpr int HK_KPT_SHIPPED = 2;          // the KPT that measured fastest on the shipped 350-gene screen
 
+// the held genes and levels of a launch, HK_CALLS_PER_LAUNCH / W rows of W entries (-1: no gene): 2 KiB at every W
+template <int W>
 struct HkCalls {
-    int g[HK_CALLS_PER_LAUNCH];
-    float v[HK_CALLS_PER_LAUNCH];
+    static constexpr int CALLS = HK_CALLS_PER_LAUNCH / W;
+    int g[CALLS * W];
+    float v[CALLS * W];
 };
 
 // hill_eval on KPT states at once: xs [KPT][N], res[j] = the rate of `gene` at state j
@@ -122,11 +132,21 @@ __device__ __forceinline__ void hill_eval_slots(const HillProg &p, int gene, con
     for (int j = 0; j < KPT; ++j) res[j] = len > 0 ? top[j] : 0.f;
 }
 
+// is `gene` one of the W held genes of a slot
+template <int W>
+__device__ __forceinline__ bool hk_held(int gene, const int (&cg)[W])
+{
+    bool held = gene == cg[0];
+#pragma unroll
+    for (int w = 1; w < W; ++w) held = held || gene == cg[w];
+    return held;
+}
+
 // calls k0 .. k0 + nk - 1 of the screen (k0: the first call of this launch), out [T, K * B, N]
-template <int KPT, int GPT>
+template <int KPT, int GPT, int W>
 __global__ __launch_bounds__(1024) void k_hill_knockouts(HillProg p, const float *__restrict__ x0,
                                                          const double *__restrict__ times, int T, double dt_max,
-                                                         HkCalls calls, int k0, int nk, int K, float *__restrict__ out,
+                                                         HkCalls<W> calls, int k0, int nk, int K, float *__restrict__ out,
                                                          int B, int N)
 {
     extern __shared__ float xs[];   // [KPT][N]
@@ -135,16 +155,19 @@ __global__ __launch_bounds__(1024) void k_hill_knockouts(HillProg p, const float
     const long long slab = (long long)K * B * N;   // floats of one output time
     for (int b = blockIdx.y; b < B; b += gridDim.y) {
         for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-            int cg[KPT];        // the clamped gene of slot j (-1: none)
-            float cv[KPT];
+            int cg[KPT][W];     // the clamped genes of slot j (-1: none)
+            float cv[KPT][W];
             bool live[KPT];     // the slot has a call: its states are stored
             float *orow[KPT];   // out[0, k * B + b, 0]
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 const int kl = grp * KPT + j;
                 live[j] = kl < nk;
-                cg[j] = live[j] ? calls.g[kl] : -1;
-                cv[j] = live[j] ? calls.v[kl] : 0.f;
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    cg[j][w] = live[j] ? calls.g[kl * W + w] : -1;
+                    cv[j][w] = live[j] ? calls.v[kl * W + w] : 0.f;
+                }
                 orow[j] = out + ((long long)(k0 + (live[j] ? kl : 0)) * B + b) * N;
             }
             float y[GPT][KPT], acc[GPT][KPT], k[GPT][KPT];
@@ -154,7 +177,9 @@ __global__ __launch_bounds__(1024) void k_hill_knockouts(HillProg p, const float
                 const float v0 = gene < N ? x0[(long long)b * N + gene] : 0.f;
 #pragma unroll
                 for (int j = 0; j < KPT; ++j) {
-                    y[g][j] = gene == cg[j] ? cv[j] : v0;
+                    y[g][j] = v0;
+#pragma unroll
+                    for (int w = 0; w < W; ++w) y[g][j] = gene == cg[j][w] ? cv[j][w] : y[g][j];
                     if (gene < N) {
                         xs[j * N + gene] = y[g][j];
                         if (live[j]) orow[j][gene] = y[g][j];
@@ -174,7 +199,7 @@ __global__ __launch_bounds__(1024) void k_hill_knockouts(HillProg p, const float
                     }
 #pragma unroll
                     for (int j = 0; j < KPT; ++j) {
-                        if (gene == cg[j]) k[g][j] = 0.f;   // the clamp: rate 0 in every stage
+                        if (hk_held<W>(gene, cg[j])) k[g][j] = 0.f;   // the clamp: rate 0 in every stage
                         acc[g][j] += wk * k[g][j];
                     }
                 }
@@ -230,13 +255,56 @@ int hillko_kpt(int N)
     return want < room ? want : room;
 }
 
-template <int KPT, int GPT>
+template <int KPT, int GPT, int W>
 hipError_t hillko_launch(dim3 grid, int threads, hipStream_t st, const HillProg &p, const float *x0, const double *times, int T,
-                         double dt_max, const HkCalls &c, int k0, int nk, int K, float *out, int B, int N)
+                         double dt_max, const HkCalls<W> &c, int k0, int nk, int K, float *out, int B, int N)
 {
-    hipLaunchKernelGGL((k_hill_knockouts<KPT, GPT>), grid, dim3(threads), sizeof(float) * (size_t)KPT * (size_t)N, st, p, x0,
-                       times, T, dt_max, c, k0, nk, K, out, B, N);
+    hipLaunchKernelGGL((k_hill_knockouts<KPT, GPT, W>), grid, dim3(threads), sizeof(float) * (size_t)KPT * (size_t)N, st, p,
+                       x0, times, T, dt_max, c, k0, nk, K, out, B, N);
     return hipGetLastError();
+}
+
+// what both entry points refuse besides their lists
+bool hillko_bad_shape(const void *code, const void *off, const void *len, const void *consts, const void *x0, const void *times,
+                      const void *genes_host, const void *values_host, const void *out, int T, double dt_max, int K, int B, int N)
+{
+    return !code || !off || !len || !consts || !x0 || !times || !genes_host || !values_host || !out || B < 1 || N < 1 || K < 1 ||
+           T < 1 || !(dt_max > 0.0) || N > HILL_GPT * 1024 || (long long)K * B > INT_MAX;
+}
+
+// the launches of a checked screen whose rows genes_host / values_host [K][width] fit W entries (width <= W: -1 pads)
+template <int W>
+int hillko_run(const HillProg &p, const float *x0, const double *times, int T, double dt_max, const int *genes_host,
+               const float *values_host, int width, int K, float *out, int B, int N, hipStream_t st)
+{
+    constexpr int CALLS = HkCalls<W>::CALLS;
+    const int gpt = hillko_gpt(N), kpt = hillko_kpt(N);
+    const int per = (N + gpt - 1) / gpt;   // genes per slot of a thread's list: N <= gpt * threads
+    const int threads = std::min(1024, ((per + 63) / 64) * 64);
+    for (int k0 = 0; k0 < K; k0 += CALLS) {
+        const int nk = K - k0 < CALLS ? K - k0 : CALLS;
+        HkCalls<W> c;
+        memset(&c, 0, sizeof(c));
+        for (int k = 0; k < nk; ++k)
+            for (int w = 0; w < W; ++w) {
+                const int g = w < width ? genes_host[(size_t)(k0 + k) * width + w] : -1;
+                c.g[k * W + w] = g;
+                c.v[k * W + w] = g >= 0 ? values_host[(size_t)(k0 + k) * width + w] : 0.f;   // the level of a pad is ignored
+            }
+        const int ngroups = (nk + kpt - 1) / kpt;
+        const dim3 grid(ngroups < HK_MAX_GRID_X ? ngroups : HK_MAX_GRID_X, B < HK_MAX_GRID_Y ? B : HK_MAX_GRID_Y);
+        hipError_t e = hipErrorInvalidValue;
+#define HK_CASE(KPT_, GPT_) \
+    if (kpt == KPT_ && gpt == GPT_) \
+        e = hillko_launch<KPT_, GPT_, W>(grid, threads, st, p, x0, times, T, dt_max, c, k0, nk, K, out, B, N)
+        HK_CASE(1, 1); HK_CASE(2, 1); HK_CASE(4, 1); HK_CASE(8, 1);
+        HK_CASE(1, 2); HK_CASE(2, 2); HK_CASE(4, 2);
+        HK_CASE(1, 4); HK_CASE(2, 4);
+        HK_CASE(1, 8);
+#undef HK_CASE
+        if (e != hipSuccess) return PHX_ERR_LAUNCH;
+    }
+    return PHX_OK;
 }
 
 }  // namespace
@@ -249,35 +317,36 @@ int phx_hill_knockouts(const int *code, const int *off, const int *len, const fl
                        const double *times, int T, double dt_max, const int *genes_host, const float *values_host, int K,
                        float *out, int B, int N, void *stream)
 {
-    if (!code || !off || !len || !consts || !x0 || !times || !genes_host || !values_host || !out || B < 1 || N < 1 || K < 1 ||
-        T < 1 || !(dt_max > 0.0) || N > HILL_GPT * 1024 || (long long)K * B > INT_MAX)
+    if (hillko_bad_shape(code, off, len, consts, x0, times, genes_host, values_host, out, T, dt_max, K, B, N))
         return PHX_ERR_BAD_ARG;
     for (int k = 0; k < K; ++k)
         if (genes_host[k] < -1 || genes_host[k] >= N || !std::isfinite(values_host[k])) return PHX_ERR_BAD_ARG;
-    hipStream_t st = (hipStream_t)stream;
     const HillProg p{reinterpret_cast<const int2 *>(code), off, len, consts};
-    const int gpt = hillko_gpt(N), kpt = hillko_kpt(N);
-    const int per = (N + gpt - 1) / gpt;   // genes per slot of a thread's list: N <= gpt * threads
-    const int threads = std::min(1024, ((per + 63) / 64) * 64);
-    for (int k0 = 0; k0 < K; k0 += HK_CALLS_PER_LAUNCH) {
-        const int nk = K - k0 < HK_CALLS_PER_LAUNCH ? K - k0 : HK_CALLS_PER_LAUNCH;
-        HkCalls c;
-        memset(&c, 0, sizeof(c));
-        memcpy(c.g, genes_host + k0, sizeof(int) * (size_t)nk);
-        memcpy(c.v, values_host + k0, sizeof(float) * (size_t)nk);
-        const int ngroups = (nk + kpt - 1) / kpt;
-        const dim3 grid(ngroups < HK_MAX_GRID_X ? ngroups : HK_MAX_GRID_X, B < HK_MAX_GRID_Y ? B : HK_MAX_GRID_Y);
-        hipError_t e = hipErrorInvalidValue;
-#define HK_CASE(KPT_, GPT_) \
-    if (kpt == KPT_ && gpt == GPT_) e = hillko_launch<KPT_, GPT_>(grid, threads, st, p, x0, times, T, dt_max, c, k0, nk, K, out, B, N)
-        HK_CASE(1, 1); HK_CASE(2, 1); HK_CASE(4, 1); HK_CASE(8, 1);
-        HK_CASE(1, 2); HK_CASE(2, 2); HK_CASE(4, 2);
-        HK_CASE(1, 4); HK_CASE(2, 4);
-        HK_CASE(1, 8);
-#undef HK_CASE
-        if (e != hipSuccess) return PHX_ERR_LAUNCH;
+    return hillko_run<1>(p, x0, times, T, dt_max, genes_host, values_host, 1, K, out, B, N, (hipStream_t)stream);
+}
+
+int phx_hill_knockout_sets(const int *code, const int *off, const int *len, const float *consts, const float *x0,
+                           const double *times, int T, double dt_max, const int *genes_host, const float *values_host,
+                           int width, int K, float *out, int B, int N, void *stream)
+{
+    if (hillko_bad_shape(code, off, len, consts, x0, times, genes_host, values_host, out, T, dt_max, K, B, N) || width < 1 ||
+        width > PHX_HILL_HOLD_MAX)
+        return PHX_ERR_BAD_ARG;
+    for (int k = 0; k < K; ++k) {
+        const int *row = genes_host + (size_t)k * width;
+        for (int w = 0; w < width; ++w) {
+            if (row[w] < -1 || row[w] >= N) return PHX_ERR_BAD_ARG;
+            if (row[w] < 0) continue;   // a pad: its level is not looked at
+            if (!std::isfinite(values_host[(size_t)k * width + w])) return PHX_ERR_BAD_ARG;
+            for (int u = 0; u < w; ++u)
+                if (row[u] == row[w]) return PHX_ERR_BAD_ARG;   // a gene twice: two levels would be ambiguous
+        }
     }
-    return PHX_OK;
+    const HillProg p{reinterpret_cast<const int2 *>(code), off, len, consts};
+    hipStream_t st = (hipStream_t)stream;
+    if (width == 1) return hillko_run<1>(p, x0, times, T, dt_max, genes_host, values_host, width, K, out, B, N, st);
+    if (width == 2) return hillko_run<2>(p, x0, times, T, dt_max, genes_host, values_host, width, K, out, B, N, st);
+    return hillko_run<4>(p, x0, times, T, dt_max, genes_host, values_host, width, K, out, B, N, st);
 }
 
 }  // extern "C"

@@ -17,6 +17,8 @@ Jacobian of the rates on its sparse pattern, the ground truth `analysis.jacobian
 And perturbed: `HillSystem.knockouts` (`phx_hill_knockouts`, `csrc/phx_hillko.hip`) integrates the system with a gene held
 at a level, `HillSystem.knockout_effects` scores such a screen as `analysis.knockout_effects` scores the model's -- the
 ground truth of `analysis.knockout_recovery`; `rates_reference` / `knockouts_reference` restate them in numpy (section 8j).
+A call may hold a SET of up to four genes (`phx_hill_knockout_sets`): `HillSystem.knockout_pairs` is the truth of
+`analysis.knockout_pairs` and its epistasis score, `analysis.epistasis_recovery` scores a model against it (section 8l).
 """
 import ast
 import collections
@@ -304,6 +306,52 @@ def _knockout_args(name, N, genes, value, lowest):
     return genes, values
 
 
+HOLD_MAX = 4     # PHX_HILL_HOLD_MAX: the genes one call of phx_hill_knockout_sets can hold
+
+
+def _entries(xs):
+    """a sequence or an array as a list whose array entries are lists"""
+    xs = xs.tolist() if hasattr(xs, "tolist") else xs
+    return [x.tolist() if hasattr(x, "tolist") else x for x in (xs if isinstance(xs, (list, tuple, range)) else [xs])]
+
+
+def _names_sets(genes):
+    """does `genes` of a knockout screen name a set anywhere (a sequence entry), or plain ints throughout"""
+    return genes is not None and any(isinstance(e, (list, tuple, range)) for e in _entries(genes))
+
+
+def _knockout_set_args(name, N, genes, value):
+    """(sets, levels) of a knockout screen with held sets: per call the tuple of its distinct genes in 0 .. N - 1, in the
+    order given (-1 entries dropped), and the tuple of their finite levels.  An entry of `genes` is an int or a sequence of
+    at most HOLD_MAX ints; `value` a scalar, or per call a scalar or a sequence as long as that call's entry"""
+    entries = _entries(genes)
+    if not entries:
+        raise ValueError("%s: no gene to hold" % name)
+    values = _entries(value) if hasattr(value, "tolist") or isinstance(value, (list, tuple)) else [value] * len(entries)
+    if len(values) != len(entries):
+        raise ValueError("%s: %d values for %d calls" % (name, len(values), len(entries)))
+    sets, levels = [], []
+    for k, (entry, level) in enumerate(zip(entries, values)):
+        held = engine.int_list(name, entry if isinstance(entry, (list, tuple, range)) else [entry])
+        engine.check_genes(name, held, N, -1)
+        if len(held) > HOLD_MAX:
+            raise ValueError("%s: call %d names %d entries, a call holds at most %d genes" % (name, k, len(held), HOLD_MAX))
+        if isinstance(level, (list, tuple)):
+            if len(level) != len(held):
+                raise ValueError("%s: call %d has %d levels for %d entries" % (name, k, len(level), len(held)))
+        else:
+            level = [level] * len(held)
+        live = [(g, float(v)) for g, v in zip(held, level) if g >= 0]
+        if len(set(g for g, _ in live)) != len(live):
+            raise ValueError("%s: call %d names a gene twice: %r" % (name, k, tuple(held)))
+        for _, v in live:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError("%s: level %r is not a finite float32" % (name, v))
+        sets.append(tuple(g for g, _ in live))
+        levels.append(tuple(v for _, v in live))
+    return sets, levels
+
+
 def _knockout_times(name, times, dt_max):
     t64 = np.ascontiguousarray(_host_times(times), np.float64).reshape(-1)
     if t64.size < 1:
@@ -382,14 +430,17 @@ class HillSystem:
         return out
 
     # ---- knockout screens
-    def _knockout_x0(self, name, x0):
-        """x0 of a knockout screen as a contiguous float32 [B, N] tensor on the system's device"""
+    def _knockout_x0(self, name, x0, host_check=None):
+        """x0 of a knockout screen as a contiguous float32 [B, N] tensor on the system's device; host_check(B): the caller's
+        ValueErrors that need B, raised before a device is asked for"""
         N = self.N
         if not isinstance(x0, torch.Tensor):
             raise TypeError("%s: x0 must be a tensor on the GPU, got %s" % (name, type(x0).__name__))
         if (x0.dtype != torch.float32 or x0.shape[0] < 1 or
                 not ((x0.dim() == 2 and x0.shape[1] == N) or (x0.dim() == 3 and x0.shape[1:] == (1, N)))):
             raise ValueError("%s: x0 must be float32 [B, %d] or [B, 1, %d], got %s %s" % (name, N, N, x0.dtype, tuple(x0.shape)))
+        if host_check is not None:
+            host_check(x0.shape[0])
         engine._require_gpu(x0, "x0")
         if self.device.type != "cuda" or x0.device != self.code.device:
             raise ValueError("%s: x0 is on %s, the system on %s" % (name, x0.device, self.device))
@@ -404,6 +455,18 @@ class HillSystem:
                                                           engine._p(out), B, self.N, engine._stream_ptr()))
         return out
 
+    def _knockout_sets(self, x2, t64, sets, levels, dt_max):
+        """phx_hill_knockout_sets on checked arguments (`_knockout_set_args`): the rows padded with -1 to the widest set"""
+        K, B, width = len(sets), x2.shape[0], max(1, max(len(s) for s in sets))
+        genes = [g for s in sets for g in s + (-1,) * (width - len(s))]
+        values = [v for l in levels for v in l + (0.0,) * (width - len(l))]
+        out = torch.empty((t64.numel(), K * B, self.N), dtype=torch.float32, device=x2.device)
+        engine._check_call(_lib.load().phx_hill_knockout_sets(*self._args(), engine._p(x2), engine._p(t64), t64.numel(),
+                                                              C.c_double(dt_max), (C.c_int * (K * width))(*genes),
+                                                              (C.c_float * (K * width))(*values), width, K, engine._p(out), B,
+                                                              self.N, engine._stream_ptr()))
+        return out
+
     def knockouts(self, x0, times, genes, value=0.0, dt_max=0.01):
         """`simulate` with a gene HELD at a level: states [T, K, B, N] float32 on the device, [:, k] the time course of the
         system started from x0 ([B, N] or [B, 1, N], float32, on the device) with column genes[k] set to value[k] and kept
@@ -412,11 +475,17 @@ class HillSystem:
         level an over-expression.  The K calls share x0 (it is not replicated) and run in one pass (phx_hill_knockouts,
         include/phoenix_hip.h): `simulate`'s integrator, several calls of a sample per workgroup.  A call's bits do not depend
         on the calls beside it, so a gene that genes[k] does not reach (`jacobian_pattern`) equals the -1 call exactly.
+        An entry of `genes` may also be a SET, a sequence of up to 4 distinct genes held together (`()` like -1: none; the
+        shape `odeint_calls(clamp=...)` accepts); value[k] is then one level for all genes of call k or a sequence matching
+        its entry.  A list with a set in it runs through phx_hill_knockout_sets, a list of plain ints as before; a call has
+        the same bits either way, in either order of its set, whatever sets stand beside it.
         Argument errors are raised on the host before any launch."""
-        genes, values = _knockout_args("knockouts", self.N, genes, value, lowest=-1)
+        sets = _names_sets(genes)
+        genes, values = (_knockout_set_args("knockouts", self.N, genes, value) if sets else
+                         _knockout_args("knockouts", self.N, genes, value, lowest=-1))
         t64, dt_max = _knockout_times("knockouts", times, dt_max)
         x2 = self._knockout_x0("knockouts", x0)
-        out = self._knockouts(x2, torch.from_numpy(t64).to(x2.device), genes, values, dt_max)
+        out = (self._knockout_sets if sets else self._knockouts)(x2, torch.from_numpy(t64).to(x2.device), genes, values, dt_max)
         return out.reshape(len(t64), len(genes), x2.shape[0], self.N)
 
     def knockout_effects(self, x0, genes=None, value=0.0, times=None, dt_max=0.01, genes_per_launch=64, want_matrices=True):
@@ -453,6 +522,67 @@ class HillSystem:
                                     magnitude=magnitude[k0:k0 + len(batch)] if want_matrices else None)
             del sol       # one output block alive at a time
         return KnockoutEffects(genes, scores.cpu().numpy(), shift, magnitude)
+
+    def coregulator_pairs(self, genes=None):
+        """The pairs that meet in a gate, on the host from `jacobian_pattern()`: the sorted list of (a, b), a < b, such that
+        the program of some third gene j (not a, not b) reads both -- where a joint knockout can be non-additive at first
+        order.  genes: only the pairs within that set of genes."""
+        pat = self.jacobian_pattern()
+        only = None if genes is None else set(engine.int_list("coregulator_pairs", genes))
+        if only is not None:
+            engine.check_genes("coregulator_pairs", sorted(only), self.N)
+        pairs = set()
+        for j in range(self.N):
+            regs = [r for r in pat.regulator[pat.ptr[j]:pat.ptr[j + 1]].tolist() if r != j and (only is None or r in only)]
+            pairs.update((a, b) for i, a in enumerate(regs) for b in regs[i + 1:])      # a row of the pattern ascends
+        return sorted(pairs)
+
+    def knockout_pairs(self, x0, genes=None, pairs=None, value=0.0, times=None, dt_max=0.01, pairs_per_launch=64,
+                       want_matrices=True, max_singles_bytes=4 << 30):
+        """The combination screen of `analysis.knockout_pairs` on the simulator itself -- the truth of that screen's epistasis
+        for a model trained on this system's data; the targets here combine their regulators through AND / OR / NOT gates, so
+        joint knockouts are non-additive.  genes / pairs / value / max_singles_bytes: the rules of `analysis.knockout_pairs`
+        (G >= 2 distinct genes and all their pairs, or explicit pairs; a scalar or one level per gene); x0, times, dt_max as
+        in `knockout_effects`.  The baseline is one -1 call and the G single-gene calls run once (phx_hill_knockouts; that
+        block stays alive); per block of `pairs_per_launch` pairs one pass of phx_hill_knockout_sets and one of
+        phx_knockout_epistasis; one pair block is alive at a time.
+        Returns the KnockoutPairs of that screen, with the meaning its fields have there.  A call's bits do not depend on
+        the calls beside it or on the width of its set, so interaction and interaction_magnitude are exactly 0 at every
+        target that is not a common descendant of both genes of a pair: where a's knockout does not reach, the pair call
+        has the bits of b's single call and a's single call those of the baseline."""
+        from .analysis import KnockoutEffects, KnockoutPairs, _knockout_pairs_args
+        N = self.N
+        genes, values, pairs, ia, ib = _knockout_pairs_args(N, genes, pairs, value, pairs_per_launch)
+        for v in values:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError("knockout_pairs: level %r is not a finite float32" % v)
+        t64, dt_max = _knockout_times("knockout_pairs", np.arange(0, 1, 0.1) if times is None else times, dt_max)
+        if len(t64) < 2 or N < 3:
+            raise ValueError("knockout_pairs: needs at least two time points and three genes")
+        G, K, T = len(genes), len(pairs), len(t64)
+
+        def singles_fit(B):
+            if 4 * T * G * B * N > max_singles_bytes:
+                raise ValueError("knockout_pairs: the block of the %d single-gene solves takes 4 T G B N = %d bytes, more than "
+                                 "max_singles_bytes = %d; screen fewer genes at a time" % (G, 4 * T * G * B * N, max_singles_bytes))
+
+        x2 = self._knockout_x0("knockout_pairs", x0, singles_fit)
+        device = x2.device
+        k_max = min(int(pairs_per_launch), K)
+        t_dev = torch.from_numpy(t64).to(device)
+        out = [torch.empty(K, dtype=torch.float32, device=device) for _ in range(2)]
+        out += [torch.empty((K, N), dtype=torch.float32, device=device) if want_matrices else None for _ in range(4)]
+        base = self._knockouts(x2, t_dev, [-1], [0.0], dt_max)                     # [T, B, N]
+        singles = self._knockouts(x2, t_dev, genes, values, dt_max)                # [T, G * B, N]
+        one = engine.knockout_effects(base, singles, genes, want_matrices=want_matrices)
+        for k0 in range(0, K, k_max):
+            k1 = min(K, k0 + k_max)
+            sol = self._knockout_sets(x2, t_dev, pairs[k0:k1], [(values[ia[k]], values[ib[k]]) for k in range(k0, k1)], dt_max)
+            engine.knockout_epistasis(base, singles, sol, ia[k0:k1], ib[k0:k1], genes,
+                                      out=[None if x is None else x[k0:k1] for x in out])
+            del sol       # one pair block alive at a time
+        return KnockoutPairs(pairs, genes, out[0].cpu().numpy(), out[1].cpu().numpy(), out[2], out[3], out[4], out[5],
+                             KnockoutEffects(genes, one[0].cpu().numpy(), one[1], one[2]))
 
     # ---- the true Jacobian
     def jacobian_pattern(self):
@@ -645,18 +775,24 @@ def knockouts_reference(system, x0, times, genes, values, dt_max, dtype=np.float
     the kernel's integrator on `rates_reference` -- classical RK4 in the kernel's order of operations, nsub = max(1,
     ceil(|span| / dt_max)) equal sub-steps of h = dtype(span / nsub) per interval -- with the clamp: call k starts with
     column genes[k] at values[k], and the rate of that column is replaced by 0 in every stage (genes[k] == -1: none).
-    x0 [B, N] or [B, 1, N]; genes / values: K ints in -1 .. N - 1 and K levels."""
+    x0 [B, N] or [B, 1, N]; genes / values: K ints in -1 .. N - 1 and K levels -- or, as in `HillSystem.knockouts`, sets of
+    up to 4 genes with a level, or a sequence of levels, per call: every column of a set starts at its level and has rate 0."""
     N = system.N
     x0 = np.asarray(x0, dtype)
     if not ((x0.ndim == 2 and x0.shape[1] == N) or (x0.ndim == 3 and x0.shape[1:] == (1, N))) or x0.shape[0] < 1:
         raise ValueError("x0 must be [B, %d] or [B, 1, %d], got %s" % (N, N, x0.shape))
-    genes, values = _knockout_args("knockouts_reference", N, genes, list(values), lowest=-1)
+    if _names_sets(genes):
+        sets, levels = _knockout_set_args("knockouts_reference", N, genes, values)
+    else:
+        genes, values = _knockout_args("knockouts_reference", N, genes, values if np.isscalar(values) else list(values), lowest=-1)
+        sets, levels = [(g,) if g >= 0 else () for g in genes], [(v,) for v in values]
     t64, dt_max = _knockout_times("knockouts_reference", times, dt_max)
-    K, B = len(genes), x0.shape[0]
+    K, B = len(sets), x0.shape[0]
     y = np.repeat(x0.reshape(1, B, N), K, axis=0)
-    held = [(k, g) for k, g in enumerate(genes) if g >= 0]
-    for k, g in held:
-        y[k, :, g] = dtype(values[k])
+    held = [(k, g) for k in range(K) for g in sets[k]]
+    for k in range(K):
+        for g, v in zip(sets[k], levels[k]):
+            y[k, :, g] = dtype(v)
 
     def f(x):
         r = rates_reference(system, x, dtype)
