@@ -554,6 +554,32 @@ int phx_effects_neighbors(const phx_params *p, int mode, const float *y, const f
                           float tau, const unsigned char *regulator_ok, const unsigned char *target_ok, int *gene, float *value,
                           unsigned *count, float *strength, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Products of a block of vectors with those matrices, taken after the same element-wise rules and without the matrices: M =
+ * what phx_effects_matrix writes for (mode, y, ph, B), entry M[i,j] eligible exactly as for phx_effects_neighbors (flags,
+ * regulator_ok, target_ok, tau and axis as there).  V and out are [N, R] row-major float, 1 <= R <= 32 per call:
+ *   PHX_NEIGHBORS_OF_TARGET      out[n, r] = sum over the eligible i of w(M[i,n]) V[i, r]    (M^T V: regulator -> target)
+ *   PHX_NEIGHBORS_OF_REGULATOR   out[n, r] = sum over the eligible j of w(M[n,j]) V[j, r]    (M V)
+ * with w the entry (PHX_APPLY_VALUE), its magnitude (PHX_APPLY_ABS) or 1.0f (PHX_APPLY_UNIT).  An ineligible entry
+ * contributes nothing -- it is skipped, not multiplied by zero -- so a non-finite entry of M never reaches out, a non-finite
+ * V[g, r] reaches only the lines with an eligible entry at gene g, and a line without an eligible entry is exactly +0.  Rows
+ * of V at or beyond N are never read.
+ * phx_apply.hip: the line-tile x segment grid of phx_neighbors.hip (S from the same rule and the same switch
+ * PHX_NEIGHBORS_SEGMENTS); lane l of each of a workgroup's four waves owns line l, wave q takes entries 16 q .. 16 q + 15 of
+ * every streamed 64 x 64 tile, whose 64 x R slice of V lies in LDS.  out[n, r] is a float sum in an order fixed by (N, S)
+ * alone: per (line, q) fmaf(w, V, acc) over the segment's streamed tiles ascending and the 16 entries of each ascending,
+ * then ((a0 + a1) + a2) + a3 over q, then the S partials in segment order (a second small kernel).  The bits of column r
+ * depend neither on R nor on where in the block the column stands.  No atomics, plain global stores; a line tile or a
+ * streamed tile without a candidate is not formed.  Nothing allocates or synchronises.
+ * PHX_ERR_BAD_ARG before any device call: everything phx_effects_neighbors refuses of (p, mode, y, ph, B, flags, axis, tau),
+ * N > 65535 included, an unknown weight, R < 1, R > 32, a null V or out.  PHX_ERR_WORKSPACE when workspace is null or
+ * workspace_bytes < phx_effects_apply_workspace_bytes(N, H, B, mode, axis, R) (the S partial blocks; 0 for arguments the
+ * call refuses; it reads the same environment switch). */
+enum phx_apply_weight { PHX_APPLY_VALUE = 0, PHX_APPLY_ABS = 1, PHX_APPLY_UNIT = 2 };
+size_t phx_effects_apply_workspace_bytes(int N, int H, int B, int mode, int axis, int R);
+int phx_effects_apply(const phx_params *p, int mode, const float *y, const float *ph, int B, int flags, int axis, int weight,
+                      float tau, const unsigned char *regulator_ok, const unsigned char *target_ok, const float *V, int R,
+                      float *out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Pathway permutation tests on one score per gene (the reference's create_permutation_test_files_aws.R, whose 500 draws per
  * pathway this call replaces).  scores [N] float; the P pathways in CSR form: ptr [P + 1] (ptr[0] = 0, non-decreasing,
  * ptr[P] = nnz) and idx [nnz], the member genes of pathway p at [ptr[p], ptr[p + 1]), each inside [0, N) and unique within

@@ -16,6 +16,7 @@ from .analysis import (Edges, EpistasisPerPair, EpistasisRecovery, EpistasisReco
                        gene_influence_scores, jacobian_matrix,
                        jacobian_recovery, knockout_effects, knockout_pairs, knockout_recovery, knockout_recovery_scores,
                        network_score,
+                       Propagation, effects_apply, network_propagation, propagation_reference,
                        pathway_permutation_test, read_network, read_pathways, recovery_scores, write_link_list,
                        write_permutation_table)
 from .simulator import (HillJacobian, HillPattern, HillSystem, generate_dataset, jacobian_reference,  # noqa: F401

@@ -43,7 +43,7 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_clamped_workspace_bytes", "phx_odeint_clamped", "phx_knockout_effects_workspace_bytes",
            "phx_knockout_effects", "phx_hill_knockouts", "phx_debug_hill_knockouts_kpt", "phx_odeint_clamped_sets",
            "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words",
-           "phx_hill_knockout_sets")
+           "phx_hill_knockout_sets", "phx_effects_apply_workspace_bytes", "phx_effects_apply")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -53,6 +53,8 @@ EDGES_ORIENT, EDGES_DIAGONAL = 1, 2                          # phx_edges_flags
 EDGES_COUNT, EDGES_EMIT = 0, 1                               # phx_edges_pass
 NEIGHBORS_AXES = {"regulator": 0, "target": 1}                # phx_neighbors_axis
 NEIGHBORS_MAX_K = 64
+APPLY_WEIGHTS = {"value": 0, "abs": 1, "unit": 2}            # phx_apply_weight
+APPLY_MAX_R = 32                                             # columns of a block of phx_effects_apply
 PATHWAYS_MAX_N = 16384                                       # phx_pathway_permutations: a gene is 14 bits of its sort key
 PATHWAYS_MAX_R = 1 << 50                                     # ... and first + n_perm stays below this
 EDGES_BINS = 4096                                            # workspace: uint32 hist[EDGES_BINS], then uint32 count
@@ -153,6 +155,10 @@ def load():
     lib.phx_effects_neighbors_workspace_bytes.restype = C.c_size_t
     lib.phx_effects_neighbors.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 4 + \
         [C.c_float, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.phx_effects_apply_workspace_bytes.argtypes = [C.c_int] * 6
+    lib.phx_effects_apply_workspace_bytes.restype = C.c_size_t
+    lib.phx_effects_apply.argtypes = [C.POINTER(PhxParams), C.c_int, vp, vp] + [C.c_int] * 4 + \
+        [C.c_float, vp, vp, vp, C.c_int, vp, vp, C.c_size_t, vp]
     lib.phx_pathway_permutations_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_longlong]
     lib.phx_pathway_permutations_workspace_bytes.restype = C.c_size_t
     lib.phx_pathway_permutations.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_longlong, C.c_ulonglong, C.c_longlong,

@@ -375,6 +375,184 @@ def effects_neighbors(odenet, k, of="target", regulators=None, targets=None, thr
                                                    threshold=threshold, orient=orient, diagonal=diagonal))
 
 
+def effects_apply(odenet, v, of="target", weight="value", regulators=None, targets=None, threshold=None, orient=False,
+                  diagonal=False, y=None, reduce="mean_abs"):
+    """The product of a block of vectors `v` ([N] or [N, R], float32, on the device) with the inferred network, without the
+    [N, N] matrix: with M = `effects_matrix(odenet)` (y=None) or `jacobian_matrix(odenet, y, reduce)`,
+        of="target":     out[n, r] = sum_i w(M[i, n]) v[i, r]     scores flow regulator -> target, M^T v
+        of="regulator":  out[n, r] = sum_j w(M[n, j]) v[j, r]     M v
+    over the eligible entries only -- the rules of `effects_neighbors`: finite, non-zero, off the diagonal unless
+    `diagonal=True`, with `orient=True` the strictly stronger direction of a gene pair, regulator in `regulators`, target in
+    `targets`, |value| >= `threshold` -- with w the entry itself (weight="value"), its magnitude ("abs") or 1 ("unit").  The
+    result has the shape of `v`, float32 on the device.  An ineligible entry is skipped, not multiplied by zero: a non-finite
+    entry of M never reaches the result, and a non-finite v[g] reaches only the lines with an eligible entry at g; a line
+    without eligible entries is +0.  Every sum has a fixed order: the result is bitwise reproducible, and a column's bits do
+    not depend on the other columns of the block.  One kernel call per 32 columns."""
+    with torch.no_grad():
+        def host_check(N):
+            checked = engine.check_apply_selection("effects_apply", of, weight, regulators, targets, threshold, N)
+            engine.check_apply_block("effects_apply", v, N)
+            return checked
+        p, mode, y2, ph, (axis, wcode, regs, tgts) = _model_states(odenet, y, reduce, host_check)
+        op = engine.ApplyOperator(p, mode, y=y2, ph=ph, regulators=regs, targets=tgts, threshold=threshold, orient=orient,
+                                  diagonal=diagonal)
+        return op.apply(v, axis, wcode)
+
+
+Propagation = collections.namedtuple("Propagation", ("score", "iterations", "residual"))
+PROPAGATION_DIRECTIONS = ("downstream", "upstream")
+PROPAGATION_WEIGHTS = ("abs", "unit")
+
+
+def propagation_steps(restart, tol):
+    """the steps after which the walk is within `tol` of its fixed point in the 1-norm, from any start on the simplex: the
+    map is a contraction with factor (1 - restart) and two distributions are at most 2 apart"""
+    return max(1, int(np.ceil(np.log(tol / 2.0) / np.log1p(-restart))))
+
+
+def _check_walk(name, N, seeds, restart, direction, weight, iterations, tol):
+    """the ValueErrors of a propagation's own arguments; returns (p0 float64 numpy [N, R] with columns that sum to 1, whether
+    the seeds were one-dimensional, the step count)"""
+    if not isinstance(direction, str) or direction not in PROPAGATION_DIRECTIONS:
+        raise ValueError('%s: direction must be "downstream" or "upstream", got %r' % (name, direction))
+    if not isinstance(weight, str) or weight not in PROPAGATION_WEIGHTS:
+        raise ValueError('%s: weight must be "abs" or "unit" (a walk has no signed weights), got %r' % (name, weight))
+    number = (int, float, np.integer, np.floating)
+    if not isinstance(restart, number) or isinstance(restart, bool) or not 0 < restart < 1:
+        raise ValueError("%s: restart must lie strictly between 0 and 1, got %r" % (name, restart))
+    if not isinstance(tol, number) or isinstance(tol, bool) or not 0 < tol < 2:
+        raise ValueError("%s: tol must be positive (and below 2), got %r" % (name, tol))
+    if iterations is not None and (not engine._is_int(iterations) or iterations < 1):
+        raise ValueError("%s: iterations must be None or an integer >= 1, got %r" % (name, iterations))
+    flat = True
+    if seeds is None:
+        p0 = np.full((N, 1), 1.0 / N)
+    else:
+        if isinstance(seeds, torch.Tensor):
+            seeds = seeds.detach().cpu().numpy()
+        try:
+            s = np.asarray(seeds if hasattr(seeds, "shape") else list(seeds))
+        except (TypeError, ValueError):
+            raise ValueError("%s: seeds must be None, a sequence of gene indices or a tensor of weights" % name)
+        if s.dtype == bool or s.dtype.kind not in "iuf":
+            raise ValueError("%s: seeds must be gene indices or non-negative weights, got dtype %s" % (name, s.dtype))
+        if s.dtype.kind in "iu" and s.ndim == 1 and not hasattr(seeds, "shape"):
+            # a plain sequence of gene indices: every listed gene gets the same weight (duplicates count once)
+            if s.size == 0 or s.min() < 0 or s.max() >= N:
+                raise ValueError("%s: seeds must be gene indices in [0, %d), and at least one" % (name, N))
+            p0 = np.zeros((N, 1))
+            p0[s, 0] = 1.0
+        else:
+            if s.ndim not in (1, 2) or s.shape[0] != N or s.size == 0:
+                raise ValueError("%s: seed weights must have the shape [%d] or [%d, R], got %s" % (name, N, N, s.shape))
+            flat = s.ndim == 1
+            p0 = s.reshape(N, -1).astype(np.float64)
+            if not np.all(np.isfinite(p0)) or p0.min() < 0:
+                raise ValueError("%s: seed weights must be finite and non-negative" % name)
+        mass = p0.sum(axis=0)
+        if np.any(mass <= 0):
+            raise ValueError("%s: seed column %d has no mass" % (name, int(np.nonzero(mass <= 0)[0][0])))
+        p0 = p0 / mass
+    return p0, flat, propagation_steps(restart, tol) if iterations is None else int(iterations)
+
+
+def _walk(apply, s, p0, restart, steps):
+    """The random walk with restart, written once for the device and for `propagation_reference`: `steps` times
+        p <- (1 - restart) (apply(p / s) + (mass of the genes with s = 0) p0) + restart p0
+    from p = p0, with `apply` the weighted sum over the edges that end (or start) at each gene and s [N, 1] the genes'
+    out- (or in-) strengths along the other axis, so that a gene hands its whole mass on, in proportion to the weights, and a
+    gene without an edge hands it back to its walk's seeds.  p0, p [N, R]: tensors or arrays, whatever `apply` takes; nothing
+    here reads a value on the host.  Returns (p, the 1-norm of the last step per column)."""
+    live = s > 0
+    dangling = 1.0 - live * 1.0
+    inv = live / (s + dangling)                  # 1 / s, and 0 where s = 0
+    p = p0
+    step = p0 - p0
+    for _ in range(steps):
+        q = (1.0 - restart) * (apply(p * inv) + (p * dangling).sum(0) * p0) + restart * p0
+        step, p = q - p, q
+    return p, abs(step).sum(0)
+
+
+def network_propagation(odenet, seeds=None, restart=0.5, direction="downstream", weight="abs", iterations=None, tol=1e-6,
+                        regulators=None, targets=None, threshold=None, orient=False, diagonal=False, y=None,
+                        reduce="mean_abs"):
+    """Network propagation on the inferred network without the [N, N] matrix: a random walk with restart,
+        p <- (1 - restart) W p + restart p0,
+    along the eligible edges of `effects_apply` (same selection arguments), weighted by their magnitude (weight="abs") or all
+    alike ("unit").  direction="downstream": a gene hands its mass to its targets, W[j, i] = w_ij / s_i with s_i = sum_j w_ij
+    its out-strength; "upstream": to its regulators, the walk on the transposed network.  A gene without an outgoing edge
+    hands its mass back to its walk's seeds.  `seeds`: None (uniform: with restart=0.15 this is PageRank on the network), a
+    sequence of gene indices, or a [N] or [N, R] tensor of non-negative weights, one walk per column; columns are scaled to
+    sum 1.  The map contracts the 1-norm by (1 - restart), so `iterations=None` takes ceil(log(tol / 2) / log(1 - restart))
+    steps, after which every walk is within `tol` of its fixed point, without a host synchronisation inside the loop.
+    Returns Propagation(score float32 [N] or [N, R] on the device, iterations, residual: the 1-norm of the last step per
+    column, read once at the end)."""
+    name = "network_propagation"
+    with torch.no_grad():
+        def host_check(N):
+            walk = _check_walk(name, N, seeds, restart, direction, weight, iterations, tol)
+            return engine.check_apply_selection(name, "target", weight, regulators, targets, threshold, N), walk
+        p, mode, y2, ph, ((_, wcode, regs, tgts), (p0, flat, steps)) = _model_states(odenet, y, reduce, host_check, name=name)
+        op = engine.ApplyOperator(p, mode, y=y2, ph=ph, regulators=regs, targets=tgts, threshold=threshold, orient=orient,
+                                  diagonal=diagonal, name=name)
+        along, across = ("target", "regulator") if direction == "downstream" else ("regulator", "target")
+        p0 = torch.from_numpy(p0.astype(np.float32)).to(p.device)
+        s = op.apply(torch.ones((p.N, 1), dtype=torch.float32, device=p.device), across, wcode)
+        score, residual = _walk(lambda x: op.apply(x, along, wcode), s, p0, restart, steps)
+        residual = residual.cpu().numpy()
+        return Propagation(score[:, 0] if flat else score, steps, residual[0] if flat else residual)
+
+
+def _eligible(M, regulators, targets, threshold, orient, diagonal):
+    """the eligibility of `effects_neighbors` on a dense float32 matrix, as a boolean [N, N]"""
+    N = M.shape[0]
+    m = np.abs(M)
+    ok = np.isfinite(m) & (m != 0)
+    eye = np.eye(N, dtype=bool)
+    if orient:
+        with np.errstate(invalid="ignore"):
+            ok &= ~eye & ~np.isnan(m.T) & (m > m.T)
+    elif not diagonal:
+        ok &= ~eye
+    if regulators is not None:
+        keep = np.zeros(N, bool)
+        keep[np.asarray(list(regulators), np.int64)] = True
+        ok &= keep[:, None]
+    if targets is not None:
+        keep = np.zeros(N, bool)
+        keep[np.asarray(list(targets), np.int64)] = True
+        ok &= keep[None, :]
+    if threshold is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= m.astype(np.float64) >= float(threshold)
+    return ok
+
+
+def propagation_reference(matrix, seeds=None, restart=0.5, direction="downstream", weight="abs", iterations=None, tol=1e-6,
+                          regulators=None, targets=None, threshold=None, orient=False, diagonal=False):
+    """`network_propagation` on a dense regulator -> target matrix (float32 [N, N], e.g. what `effects_matrix` returned,
+    brought to the host), in numpy float64 and without a GPU: the same walk (`_walk`), with the edge sums taken on the
+    matrix.  Propagation(score float64 [N] or [N, R], iterations, residual)."""
+    name = "propagation_reference"
+    M = np.asarray(matrix)
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] < 2:
+        raise ValueError("%s: the matrix must be [N, N] with N >= 2, got %s" % (name, M.shape))
+    N = M.shape[0]
+    p0, flat, steps = _check_walk(name, N, seeds, restart, direction, weight, iterations, tol)
+    _, _, regs, tgts = engine.check_apply_selection(name, "target", weight, regulators, targets, threshold, N)
+    ok = _eligible(M.astype(np.float32), None if regs is None else regs.tolist(), None if tgts is None else tgts.tolist(),
+                   threshold, orient, diagonal)
+    W = np.zeros((N, N))
+    W[ok] = 1.0 if weight == "unit" else np.abs(M[ok]).astype(np.float64)
+    if direction == "downstream":                 # along the columns: the regulators' mass arrives at their targets
+        s, apply = W.sum(axis=1)[:, None], lambda x: W.T @ x
+    else:
+        s, apply = W.sum(axis=0)[:, None], lambda x: W @ x
+    score, residual = _walk(apply, s, p0, restart, steps)
+    return Propagation(score[:, 0] if flat else score, steps, residual[0] if flat else residual)
+
+
 def write_link_list(fp, edges, gene_names=None, signed=False, of=None):
     """Writes the reference's ranked link-list file (get_link_list, GRN_rnaode.py:140-163): one line "regulator<TAB>target<TAB>
     score" per link, the score as %.6f.  `edges`: an `Edges`, written in its order, or a `Neighbors` together with the `of` it

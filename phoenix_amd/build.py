@@ -35,9 +35,9 @@ PROF_LIB = os.path.join(HERE, "libphoenix_prof.so")
 PROF_UNITS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_adj2.hip")
 # Units whose device assembly is also written to csrc/_obj/<unit>.s: every kernel that stores through buffer resources
 # (the store-data hazard is checked on these listings, tools/check_store_hazard.py); phx_neighbors.hip stores plainly and
-# is listed so that the check sees that
+# and phx_apply.hip store plainly and are listed so that the check sees that
 LISTINGS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_fwd3c.hip", "phx_adj3c.hip", "phx_bp.hip", "phx_effects.hip",
-            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip", "phx_adj3t.hip")
+            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip", "phx_adj3t.hip", "phx_apply.hip")
 
 
 def sources():

@@ -1,5 +1,5 @@
 // phx_effects_tile.inc -- the 64 x 64 tile engine shared by phx_effects.hip (which stores the tile) and its epilogue units
-// phx_edges.hip, phx_netscore.hip and phx_neighbors.hip (which select from it): the LDS image, the K loops and
+// phx_edges.hip, phx_netscore.hip, phx_neighbors.hip (which select from it) and phx_apply.hip (which sums it): the LDS image, the K loops and
 // efx_tile<MODE>, which leaves one finished tile of the regulator -> target matrix in the MFMA accumulator layout, and
 // behind them what the units share around the tile: the block-to-tile decoding, the parked tile, the tile pair of the
 // oriented kernels, the argument checks and the <MODE, ORIENT> launch dispatch.  Included inside an anonymous namespace

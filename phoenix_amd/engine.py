@@ -1005,6 +1005,19 @@ def _gene_set(name, what, x, N):
     return x
 
 
+def _gene_masks(sets, N, device):
+    """the candidate lists of `_gene_set` as byte masks [N] on the device (None stays None: every gene)"""
+    masks = []
+    for idx in sets:
+        if idx is None:
+            masks.append(None)
+        else:
+            m = torch.zeros(N, dtype=torch.uint8, device=device)
+            m[idx.to(device)] = 1
+            masks.append(m)
+    return masks
+
+
 def check_neighbors_selection(k, of, regulators, targets, threshold, N):
     """the ValueErrors of the selection arguments of `effects_neighbors`, raised before a device is needed: (k, axis,
     regulators, targets) with the candidate lists as int64 tensors or None"""
@@ -1033,14 +1046,7 @@ def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=
         if tau is None:                                   # above every finite float32: nothing is eligible
             return (torch.full((N, k), -1, dtype=torch.int64, device=dev), torch.zeros((N, k), dtype=torch.float32, device=dev),
                     torch.zeros(N, dtype=torch.int64, device=dev), torch.zeros(N, dtype=torch.float32, device=dev))
-    masks = []
-    for idx in (regulators, targets):
-        if idx is None:
-            masks.append(None)
-        else:
-            m = torch.zeros(N, dtype=torch.uint8, device=dev)
-            m[idx.to(dev)] = 1
-            masks.append(m)
+    masks = _gene_masks((regulators, targets), N, dev)
     lib = _lib.load()
     nbytes = lib.phx_effects_neighbors_workspace_bytes(N, H, B, _lib.EFFECTS_MODES[mode], axis, k)
     ws = _analysis_workspace(OP_NEIGHBORS, nbytes, dev)
@@ -1054,6 +1060,90 @@ def effects_neighbors(params, mode, k, of="target", y=None, ph=None, regulators=
                                           _p(masks[0]), _p(masks[1]), _p(gene), _p(value), _p(count), _p(strength), _p(ws),
                                           nbytes, _stream_ptr()))
     return gene.to(torch.int64), value, count.to(torch.int64), strength
+
+
+OP_APPLY = 14        # workspace-cache key of effects_apply (phx_effects_apply_workspace_bytes sizes it)
+
+
+def check_apply_selection(name, of, weight, regulators, targets, threshold, N):
+    """the ValueErrors of the selection arguments of `effects_apply` (and of the walks on it), raised before a device is
+    needed: (axis, weight code, regulators, targets) with the candidate lists as int64 tensors or None"""
+    if not isinstance(of, str) or of not in _lib.NEIGHBORS_AXES:
+        raise ValueError('%s: of must be "target" or "regulator", got %r' % (name, of))
+    if not isinstance(weight, str) or weight not in _lib.APPLY_WEIGHTS:
+        raise ValueError('%s: weight must be "value", "abs" or "unit", got %r' % (name, weight))
+    _check_threshold(name, threshold)
+    return (_lib.NEIGHBORS_AXES[of], _lib.APPLY_WEIGHTS[weight], _gene_set(name, "regulators", regulators, N),
+            _gene_set(name, "targets", targets, N))
+
+
+def check_apply_block(name, v, N):
+    """ValueError unless `v` is a tensor of shape [N] or [N, R] with R >= 1"""
+    if not isinstance(v, torch.Tensor) or v.dim() not in (1, 2) or v.shape[0] != N or v.numel() == 0:
+        raise ValueError("%s: v must be a tensor of shape [%d] or [%d, R] with R >= 1, got %s"
+                         % (name, N, N, tuple(v.shape) if isinstance(v, torch.Tensor) else type(v).__name__))
+
+
+class ApplyOperator:
+    """The matrix `effects_matrix(params, mode, y, ph)` would return, filtered by the eligibility rules of
+    `effects_neighbors` (include/phoenix_hip.h), as an operator on blocks of vectors: prepared once -- the states, the
+    candidate masks and the threshold are checked and laid out here, with the host reads that takes -- and applied any
+    number of times without a host synchronisation (phx_effects_apply; the matrix is never formed).  `regulators` and
+    `targets` are what `_gene_set` returned."""
+
+    def __init__(self, params, mode, y=None, ph=None, regulators=None, targets=None, threshold=None, orient=False,
+                 diagonal=False, name="effects_apply"):
+        _check_threshold(name, threshold)
+        self.y, self.ph, self.B = _effects_states(name, params, mode, y, ph, pairs=True)
+        self.params, self.mode, self.name = params, _lib.EFFECTS_MODES[mode], name
+        self.tau = 0.0 if threshold is None else _edges_tau(float(threshold))     # None: above every finite float32
+        self.masks = _gene_masks((regulators, targets), params.N, params.device)
+        self.flags = _edges_flags(orient, diagonal)
+
+    def apply(self, v, axis, weight):
+        """out[n, r] = sum over the eligible entries of line n (column n of the matrix with axis "target", row n with
+        "regulator") of w(entry) * v[other gene, r], w the entry ("value"), its magnitude ("abs") or 1 ("unit"): float32, of
+        the shape of `v` ([N] or [N, R]).  Blocks of more than 32 columns are served 32 at a time."""
+        N, H, dev = self.params.N, self.params.H, self.params.device
+        check_apply_block(self.name, v, N)
+        _require_f32(v, "v")
+        if v.device != dev:
+            raise ValueError("%s: v must be on the parameters' device" % self.name)
+        axis = _lib.NEIGHBORS_AXES.get(axis, axis)
+        weight = _lib.APPLY_WEIGHTS.get(weight, weight)
+        v2 = v.detach().reshape(N, -1)
+        R = v2.shape[1]
+        if self.tau is None:                              # nothing is eligible
+            return torch.zeros_like(v, dtype=torch.float32)
+        lib = _lib.load()
+        p = self.params.on_current_stream()
+        out = torch.empty((N, R), dtype=torch.float32, device=dev)
+        for c0 in range(0, R, _lib.APPLY_MAX_R):
+            c1 = min(R, c0 + _lib.APPLY_MAX_R)
+            whole = c0 == 0 and c1 == R
+            vb = (v2 if whole else v2[:, c0:c1]).contiguous()
+            ob = out if whole else torch.empty((N, c1 - c0), dtype=torch.float32, device=dev)
+            nbytes = lib.phx_effects_apply_workspace_bytes(N, H, self.B, self.mode, axis, c1 - c0)
+            ws = _analysis_workspace(OP_APPLY, nbytes, dev)
+            _check_call(lib.phx_effects_apply(C.byref(p.c), self.mode, _p(self.y), _p(self.ph), self.B, self.flags, axis,
+                                              weight, self.tau, _p(self.masks[0]), _p(self.masks[1]), _p(vb), c1 - c0,
+                                              _p(ob), _p(ws), nbytes, _stream_ptr()))
+            if not whole:
+                out[:, c0:c1] = ob
+        return out.reshape(v.shape)
+
+
+def effects_apply(params, mode, v, of="target", weight="value", y=None, ph=None, regulators=None, targets=None, threshold=None,
+                  orient=False, diagonal=False):
+    """phx_effects_apply on laid-out parameters (`Params`): the product of the block `v` ([N] or [N, R] float32 on the
+    device) with the eligible entries of the matrix `effects_matrix(params, mode, y, ph)` would return, along its columns
+    (of="target": M^T v) or its rows (of="regulator": M v); see `ApplyOperator`."""
+    axis, weight, regulators, targets = check_apply_selection("effects_apply", of, weight, regulators, targets, threshold,
+                                                              params.N)
+    check_apply_block("effects_apply", v, params.N)
+    op = ApplyOperator(params, mode, y=y, ph=ph, regulators=regulators, targets=targets, threshold=threshold, orient=orient,
+                       diagonal=diagonal)
+    return op.apply(v, axis, weight)
 
 
 OP_PATHWAYS = 10     # workspace-cache key of pathway_permutations (phx_pathway_permutations_workspace_bytes sizes it)
