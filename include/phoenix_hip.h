@@ -158,6 +158,35 @@ int phx_odeint_clamped(const phx_params *p, const float *y0, const double *t, in
 int phx_odeint_clamped_sets(const phx_params *p, const float *y0, const double *t, int B, int T, const phx_solve_opts *opts,
                             const int *clamp_genes, int width, float *sol, int *status, int *nfe, int *nsteps,
                             void *workspace, size_t workspace_bytes, void *stream);
+/* Perturbation time courses to TRAIN on (additive, ABI 7): a held set per trajectory ROW, forward and adjoint, under
+ * PHX_CTRL_PER_TRAJECTORY (t [T], or [B, T] with t_per_sample).  clamp_genes is DEVICE, [B, width] row-major,
+ * 1 <= width <= PHX_CLAMP_MAX: row b of y0 holds every gene of row b of the list for its whole time course, the empty set
+ * (all entries -1) being an unperturbed sample.  Definition, arithmetic included: row b is solved with the model whose g
+ * is 0 on its set -- forward d y[b, k] / dt = 0 on the set; backward the continuous adjoint of that per-row model:
+ * q = a relu(g) and k_y are 0 at a held gene, a[k] still evolves (adj_y0[b, k] is dL/d(level the gene is held at)), and
+ * g[k] and row k of W_alpha receive nothing from that row.  grads (+)= the sum over the rows, under phx_grads.overwrite
+ * like phx_odeint_adjoint_backward.  The parameters are never modified.  Entries no gene has (-1, >= N) match nothing
+ * and pad a set; the list is not validated on the device.
+ * Served by the CLAMP forms of k1_solve_fwd3 and k1_solve_adj3 (H <= 48; the backward launch runs without the tail
+ * kernel); a batch of more rows than one launch holds goes through the shared chunk driver, the list offset by
+ * width x rows together with the y0 / sol / t rows.  phx_odeint_clamped_rows_workspace_bytes (op = PHX_OP_ODEINT or
+ * PHX_OP_ADJOINT) is 0 exactly where the launch is not served -- H > 48, PHX_ENGINE=v0, a shape the narrow kernels do not
+ * plan -- and plans for 256 CUs when no device is visible.  Both entry points return PHX_ERR_BAD_ARG before any device
+ * call for a null list (or any pointer the unclamped entry point refuses), width < 1, width > PHX_CLAMP_MAX, a method
+ * other than dopri5, control other than PHX_CTRL_PER_TRAJECTORY, and a shape whose size query is 0: solve such batches
+ * group by group with g zeroed on each set. */
+size_t phx_odeint_clamped_rows_workspace_bytes(int op, int N, int H, int B, int T);
+int phx_odeint_clamped_rows(const phx_params *p, const float *y0, const double *t, int B, int T, const phx_solve_opts *opts,
+                            const int *clamp_genes, int width, float *sol, int *status, int *nfe, int *nsteps,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int phx_odeint_adjoint_backward_clamped_rows(const phx_params *p, const double *t, int B, int T, const phx_solve_opts *opts,
+                                             const int *clamp_genes, int width, const float *y_saved, const float *grad_y,
+                                             float *adj_y0, const phx_grads *grads, int *status, int *nfe, int *nsteps,
+                                             void *workspace, size_t workspace_bytes, void *stream);
+/* diagnostic: the first launch of such a batch, planned for 256 CUs when no device is visible.  plan[8] = {kernel id (3),
+ * HALF form, SPLIT form, rows per launch, launches, batch groups TG, gene-tile groups G, trajectory tiles per group};
+ * returns 0 (plan zeroed) where the size query is 0. */
+int phx_debug_clamped_rows_plan(int op, int N, int H, int B, int T, int *plan);
 
 /* Replaces ODENet.forward / prior_only_forward (odenet.py:85-98): out[B,N] = f(y[B,N]). */
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only,

@@ -43,7 +43,9 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_clamped_workspace_bytes", "phx_odeint_clamped", "phx_knockout_effects_workspace_bytes",
            "phx_knockout_effects", "phx_hill_knockouts", "phx_debug_hill_knockouts_kpt", "phx_odeint_clamped_sets",
            "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words",
-           "phx_hill_knockout_sets", "phx_effects_apply_workspace_bytes", "phx_effects_apply")
+           "phx_hill_knockout_sets", "phx_effects_apply_workspace_bytes", "phx_effects_apply",
+           "phx_odeint_clamped_rows_workspace_bytes", "phx_odeint_clamped_rows",
+           "phx_odeint_adjoint_backward_clamped_rows", "phx_debug_clamped_rows_plan")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -180,6 +182,15 @@ def load():
                                            C.c_int, vp, C.c_int, C.c_int, vp]
     lib.phx_odeint_clamped_sets.argtypes = [C.POINTER(PhxParams), vp, vp, C.c_int, C.c_int, C.POINTER(PhxSolveOpts), vp,
                                             C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    # (an earlier build of ABI 7 named by PHX_LIB for an A/B timing of the unclamped paths has no per-row clamp)
+    if path == _build.LIB or hasattr(lib, "phx_odeint_clamped_rows"):
+        lib.phx_odeint_clamped_rows_workspace_bytes.argtypes = [C.c_int] * 5
+        lib.phx_odeint_clamped_rows_workspace_bytes.restype = C.c_size_t
+        lib.phx_odeint_clamped_rows.argtypes = lib.phx_odeint_clamped_sets.argtypes
+        lib.phx_odeint_adjoint_backward_clamped_rows.argtypes = [C.POINTER(PhxParams), vp, C.c_int, C.c_int,
+                                                                 C.POINTER(PhxSolveOpts), vp, C.c_int, vp, vp, vp,
+                                                                 C.POINTER(PhxGrads), vp, vp, vp, vp, C.c_size_t, vp]
+        lib.phx_debug_clamped_rows_plan.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
     lib.phx_knockout_epistasis_workspace_bytes.argtypes = [C.c_int] * 5
     lib.phx_knockout_epistasis_workspace_bytes.restype = C.c_size_t
     lib.phx_knockout_epistasis.argtypes = ([vp] * 3 + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 3 + [vp] * 7 +

@@ -26,6 +26,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # every build by tools/check_store_hazard.py (tests/test_abi_cpu.py runs it on the listings build() leaves in _obj/).
 UNIT_FLAGS = {"phx_fwd3.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
               "phx_fwd3k.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # the same kernel: the same flag
+              "phx_fwd3r.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],   # (phx_adj3r.hip: phx_adj3.hip's default)
               "phx_adj2.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
               "phx_v1.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
 # Diagnostic build (PHX_PROF=2: per-block timers inside the sweeps of the third-generation kernels): the marks are compiled
@@ -37,7 +38,8 @@ PROF_UNITS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_adj2.hip")
 # (the store-data hazard is checked on these listings, tools/check_store_hazard.py); phx_neighbors.hip stores plainly and
 # and phx_apply.hip store plainly and are listed so that the check sees that
 LISTINGS = ("phx_fwd3.hip", "phx_adj3.hip", "phx_fwd3c.hip", "phx_adj3c.hip", "phx_bp.hip", "phx_effects.hip",
-            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip", "phx_adj3t.hip", "phx_apply.hip")
+            "phx_neighbors.hip", "phx_fwd3k.hip", "phx_fwd3ck.hip", "phx_adj3t.hip", "phx_apply.hip", "phx_fwd3r.hip",
+            "phx_adj3r.hip")
 
 
 def sources():

@@ -28,18 +28,10 @@ size_t lds_bytes_adj3(const D1 &d)
 // plan_resident for dopri5 with H <= 48: one wave per SIMD (the augmented sweeps need the 512-register budget)
 bool plan_adj3(const Shape &s, D1 *out)
 {
-    if (s.cus <= 0 || s.calls > 1 || s.method != PHX_DOPRI5 || s.H > 48) return false;
     const Switches sw = read_switches(SW_ADJ | SW_V3_NB);
-    if (sw.v0 || sw.adj == 1 || sw.adj == 2) return false;
-    const int HT = 3;
+    if (sw.adj == 1 || sw.adj == 2) return false;
     D1 best;
-    // (control LDS + that of the block-split combine where the batch is that small: v3_split_parts)
-    if (!plan_resident(s, make_tiles(HT, 1, s.H, NVEC_ADJ3), 4, 0, sw.v3_nb,
-                       [&](int NW, int TPW, int TG, int ntg, int Bt) {
-                           return ((ctl3_bytes(Bt, ntg) + 15) & ~(size_t)15) +
-                                  (v3_split_parts(TG, NW, TPW, ntg) > 1 ? v3_comb_bytes(NW, 4 * HT) : 0);
-                       }, &best))
-        return false;
+    if (!plan_adj3_any(s, &best)) return false;
     // by shape: the many-member exchange of a narrow hidden layer (the breast-cancer shape) is this kernel's; groups of
     // up to 32 gene tiles stay with the wave-pair kernel (k1_solve_adj2), which is faster there.  PHX_ADJ=v3 forces it.
     if (sw.adj != 3 && best.G <= 32) return false;
@@ -86,7 +78,7 @@ hipError_t launch_adj3(const void *fn, const SolveArgs &a, hipStream_t st)
     // PHX_PROF=2: + per-block timers of the sweeps, 3: + of the quadrature; 8: k3_tail_adj3 follows (reduce_adj3)
     const int flags = a.grads | (a.w.prof_level == 2 ? 2 : 0) | (a.w.prof_level == 3 ? 4 : 0) | (adj3_tail_on(a) ? 8 : 0);
     return launch_persistent(fn, dim3(a.d.TG * a.d.G), dim3(64 * a.d.NW), a.lds, st, a.net, a.d, a.w, a.cfg, a.t, a.y_saved,
-                             a.grad_y, a.adj_y0, a.status, a.nfe, a.nsteps, flags, a.PP);
+                             a.grad_y, a.adj_y0, a.status, a.nfe, a.nsteps, flags, a.PP, (const int *)nullptr, 1);   // (no list)
 }
 
 bool reduce_adj3(const SolveArgs &a, int npart, const phx_grads *g, int overwrite, hipStream_t st)
@@ -104,6 +96,21 @@ bool reduce_adj3(const SolveArgs &a, int npart, const phx_grads *g, int overwrit
 }  // namespace
 
 namespace phxh {
+// the launch k1_solve_adj3 takes, whatever the group size (plan_adj3 adds the choice against k1_solve_adj2)
+bool plan_adj3_any(const Shape &s, D1 *out)
+{
+    if (s.cus <= 0 || s.calls > 1 || s.method != PHX_DOPRI5 || s.H > 48) return false;
+    const Switches sw = read_switches(SW_ADJ | SW_V3_NB);
+    if (sw.v0) return false;
+    const int HT = 3;
+    // (control LDS + that of the block-split combine where the batch is that small: v3_split_parts)
+    return plan_resident(s, make_tiles(HT, 1, s.H, NVEC_ADJ3), 4, 0, sw.v3_nb,
+                         [&](int NW, int TPW, int TG, int ntg, int Bt) {
+                             return ((ctl3_bytes(Bt, ntg) + 15) & ~(size_t)15) +
+                                    (v3_split_parts(TG, NW, TPW, ntg) > 1 ? v3_comb_bytes(NW, 4 * HT) : 0);
+                         }, out);
+}
+
 const Backend &adj3_backend()
 {
     static const Backend b = {3, true, false, true, plan_adj3, make_layout3, lds_bytes_adj3, plan6_ht, prepare_adj3,

@@ -1078,7 +1078,8 @@ int run_solve(const Pick &k, int cus, const SolveCall &c)
         // a clamped launch of ONE call (calls == 1, or the remainder of a chunked batch) is planned like an ordinary
         // shared-control launch and still runs the CALLS form, which alone reads the list: one group of Bcall rows
         if (c.clamp && d.Bcall == 0) d.Bcall = c.Bcall;
-        a.clamp = c.clamp ? c.clamp + (size_t)c.clamp_width * (c.Bcall > 0 ? b0 / c.Bcall : 0) : nullptr;
+        // (a list per call moves with the calls; a list per trajectory row -- no calls -- with the rows)
+        a.clamp = c.clamp ? c.clamp + (size_t)c.clamp_width * (c.Bcall > 0 ? b0 / c.Bcall : b0) : nullptr;
         a.clamp_width = c.clamp_width;
         const long long r0 = (long long)b0 * p->N;
         auto rows = [&](auto *q) { return q ? q + r0 : q; };
@@ -1816,6 +1817,89 @@ int phx_odeint_clamped(const phx_params *p, const float *y0_all, const double *t
 {
     return phx_odeint_clamped_sets(p, y0_all, t_all, B, T, o, clamp_gene, 1, sol_all, status_all, nfe_all, nsteps_all,
                                    workspace, workspace_bytes, stream);
+}
+
+// ---- a held set per trajectory ROW under per-trajectory control, forward and adjoint: the narrow third-generation
+// kernels (k1_solve_fwd3 / k1_solve_adj3, H <= 48) at every shape their planners lay out, in chunks like any
+// per-trajectory batch
+static Pick pick_clamped_rows(int op, int cus, int N, int H, int B, int T)
+{
+    if (N <= 0 || H <= 0 || B <= 0 || T < 0 || (op != PHX_OP_ODEINT && op != PHX_OP_ADJOINT)) return {nullptr, 0};
+    const Backend &be = op == PHX_OP_ODEINT ? fwd3_backend() : adj3_rows_backend();
+    const int chunk = pick_chunk(be, cus, N, H, B, T, PHX_CTRL_PER_TRAJECTORY, PHX_DOPRI5);
+    return chunk > 0 ? Pick{&be, chunk} : Pick{nullptr, 0};
+}
+
+size_t phx_odeint_clamped_rows_workspace_bytes(int op, int N, int H, int B, int T)
+{
+    const int cus = cus_or_mi355x(num_cus());
+    const Pick k = pick_clamped_rows(op, cus, N, H, B, T);
+    return k.be ? launches_bytes(*k.be, cus, N, H, B, k.chunk, T, PHX_CTRL_PER_TRAJECTORY, PHX_DOPRI5, true) : 0;
+}
+
+int phx_debug_clamped_rows_plan(int op, int N, int H, int B, int T, int *plan)
+{
+    if (plan)
+        for (int i = 0; i < 8; ++i) plan[i] = 0;
+    const int cus = cus_or_mi355x(num_cus());
+    const Pick k = pick_clamped_rows(op, cus, N, H, B, T);
+    D1 d;
+    if (!k.be || !plan_rows(*k.be, cus, N, H, std::min(k.chunk, B), T, PHX_CTRL_PER_TRAJECTORY, PHX_DOPRI5, 0, &d)) return 0;
+    if (plan) {
+        const char *eh = getenv("PHX_V3_HALF");
+        const int v[8] = {k.be->id, (H <= 16 * (d.HT - 1) + 8 && !(eh && eh[0] == '0')) ? 1 : 0,
+                          (d.TG == 1 && d.TPW == 1 && d.ntg * 2 <= d.NW) ? 1 : 0 /* v3_split_parts > 1 */, k.chunk, (B + k.chunk - 1) / k.chunk, d.TG, d.G,
+                          d.ntg};
+        for (int i = 0; i < 8; ++i) plan[i] = v[i];
+    }
+    return 1;
+}
+
+// the refusals both entry points share, all before any device call
+static bool bad_clamped_rows(int op, const phx_params *p, int B, int T, const phx_solve_opts *o, const int *clamp_genes,
+                             int width)
+{
+    if (bad_params(p) || !o || !clamp_genes || B <= 0 || T < 1 || width < 1 || width > PHX_CLAMP_MAX) return true;
+    if (o->method != PHX_DOPRI5 || o->control != PHX_CTRL_PER_TRAJECTORY || o->calls > 1) return true;
+    return phx_odeint_clamped_rows_workspace_bytes(op, p->N, p->H, B, T) == 0;
+}
+
+int phx_odeint_clamped_rows(const phx_params *p, const float *y0_all, const double *t_all, int B, int T,
+                            const phx_solve_opts *o, const int *clamp_genes, int width, float *sol_all, int *status_all,
+                            int *nfe_all, int *nsteps_all, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!y0_all || !t_all || !sol_all || !status_all || !nfe_all || !nsteps_all || !workspace ||
+        bad_clamped_rows(PHX_OP_ODEINT, p, B, T, o, clamp_genes, width))
+        return PHX_ERR_BAD_ARG;
+    const int cus = num_cus();
+    if (cus <= 0) return PHX_ERR_LAUNCH;
+    const Pick k = pick_clamped_rows(PHX_OP_ODEINT, cus, p->N, p->H, B, T);
+    if (!k.be) return PHX_ERR_BAD_ARG;
+    SolveCall c{p, o, B, T, t_all, y0_all, nullptr, nullptr, sol_all, nullptr, status_all, nfe_all, nsteps_all, nullptr,
+                workspace, workspace_bytes, (hipStream_t)stream};
+    c.clamp = clamp_genes;
+    c.clamp_width = width;
+    return run_solve(k, cus, c);
+}
+
+int phx_odeint_adjoint_backward_clamped_rows(const phx_params *p, const double *t_all, int B, int T, const phx_solve_opts *o,
+                                             const int *clamp_genes, int width, const float *y_saved_all,
+                                             const float *grad_y_all, float *adj_y0_all, const phx_grads *grads,
+                                             int *status_all, int *nfe_all, int *nsteps_all, void *workspace,
+                                             size_t workspace_bytes, void *stream)
+{
+    if (!t_all || !y_saved_all || !grad_y_all || !adj_y0_all || !status_all || !nfe_all || !nsteps_all || !workspace ||
+        bad_grads(grads) || bad_clamped_rows(PHX_OP_ADJOINT, p, B, T, o, clamp_genes, width))
+        return PHX_ERR_BAD_ARG;
+    const int cus = num_cus();
+    if (cus <= 0) return PHX_ERR_LAUNCH;
+    const Pick k = pick_clamped_rows(PHX_OP_ADJOINT, cus, p->N, p->H, B, T);
+    if (!k.be) return PHX_ERR_BAD_ARG;
+    SolveCall c{p, o, B, T, t_all, nullptr, y_saved_all, grad_y_all, nullptr, adj_y0_all, status_all, nfe_all, nsteps_all,
+                grads, workspace, workspace_bytes, (hipStream_t)stream};
+    c.clamp = clamp_genes;
+    c.clamp_width = width;
+    return run_solve(k, cus, c);
 }
 
 int phx_rhs_forward(const phx_params *p, const float *y, float *out, int B, int prior_only, void *workspace,

@@ -61,7 +61,8 @@ const void *prepare_fwd3(SolveArgs &a, const phx_params *p, hipStream_t st)
     const char *et = getenv("PHX_V3_TERM");   // diagnostic: 0 = no terminal tiles, every step ends with the accept pass
     a.w.prof_level = (a.w.prof_level & 0xff) | ((et && et[0] == '0') ? FWD3_NO_TERM : 0);
     const bool split = v3_split_parts(d.TG, d.NW, d.TPW, d.ntg) > 1;   // small batch: the waves of a tile split its blocks
-    if (a.clamp) return d.Bcall > 0 ? fwd3_clamp_kernel(half) : nullptr;   // held genes per call (phx_fwd3k.hip)
+    // held genes per call (phx_fwd3k.hip), or per trajectory row under per-trajectory control (phx_fwd3r.hip)
+    if (a.clamp) return d.Bcall > 0 ? fwd3_clamp_kernel(half) : fwd3_rows_kernel(half, split);
     if (d.Bcall > 0)   // several calls, a time row each (one call alone is an ordinary shared-control launch)
         return half ? reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, true, false, true>)
                     : reinterpret_cast<const void *>(k1_solve_fwd3<3, 256, false, false, true>);

@@ -238,4 +238,13 @@ bool launch_adj3_tail(const SolveArgs &a, const phx_grads *g, int overwrite, hip
 const void *fwd3_clamp_kernel(bool half);
 const void *fwd3c_clamp_kernel(int nbt, bool half, bool hb);
 
+// the CLAMP forms with a held set per trajectory ROW (phx_odeint_clamped_rows, phx_odeint_adjoint_backward_clamped_rows),
+// in units of their own too: k1_solve_fwd3's (phx_fwd3r.hip; phx_fwd3.hip's backend launches them) and k1_solve_adj3's
+// (phx_adj3r.hip), which come with a backend of their own -- k1_solve_adj3 at EVERY shape its planner lays out, also the
+// small gene-tile groups that an unclamped solve leaves to k1_solve_adj2, and always without the tail kernel
+const void *fwd3_rows_kernel(bool half, bool split);
+const Backend &adj3_rows_backend();
+// phx_adj3.hip's planner without its choice between k1_solve_adj3 and k1_solve_adj2
+bool plan_adj3_any(const Shape &s, D1 *out);
+
 }  // namespace phxh

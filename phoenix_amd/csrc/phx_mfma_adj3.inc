@@ -107,11 +107,19 @@ __global__ __launch_bounds__(256) void k3_reduce_grads(const float *__restrict__
     }
 }
 
-template <int HT, bool HALF, bool SPLIT>
+// CLAMP (phx_odeint_adjoint_backward_clamped_rows; the forms of phx_adj3r.hip): trajectory row b holds the genes
+// clamp_gene[b * clamp_width .. + clamp_width) (at most PHX_CLAMP_MAX; an index no gene has pads a set) -- its adjoint
+// is that of the model with g = 0 on the set.  A lane reads relu(g) of its trajectory's held genes as 0 wherever the
+// multipliers enter: in the sweep body (vjp, k_y, q), and in the quadrature visit on q inside the trajectory-tile loop
+// (the multipliers themselves are loaded once per half block, for all tiles).  dg needs no mask of its own: its term is
+// a * k_y / relu(g) with the stored k_y, which the masked sweep left at 0 for a held gene.  The sets are read per tile
+// visit into vector registers (clamp_set_row).  Without CLAMP the two trailing arguments are never read.
+template <int HT, bool HALF, bool SPLIT, bool CLAMP = false>
 __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveCfg cfg, const double *__restrict__ t,
                                                      const float *__restrict__ y_saved,
                                                      const float *__restrict__ grad_y, float *adj_y0, int *status,
-                                                     int *nfe_out, int *nsteps_out, int want_grads_flags, long long PP)
+                                                     int *nfe_out, int *nsteps_out, int want_grads_flags, long long PP,
+                                                     const int *__restrict__ clamp_gene, int clamp_width)
 {
     const int want_grads = want_grads_flags & 1;
     const bool prof_sweep = (want_grads_flags & 2) != 0, prof_quad = (want_grads_flags & 4) != 0;   // PHX_PROF=2 / 3
@@ -508,6 +516,8 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
             const int lb = ttl * 16 + li;
             const int b = grp * Bt + lb;
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
+            ClampSet rset{};   // the held genes of the lane's trajectory row
+            if constexpr (CLAMP) rset = clamp_set_row(clamp_gene, b, B, clamp_width);
             bool hq_dirty = false;   // this wave wrote shared transposed rows: drained before its next publication
             float ty0[8], ta0[8], tky[NKL][8], tka[NKL][8];
             auto issue = [&](int bl) {
@@ -654,6 +664,11 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
                 float rr[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) rr[j] = rg[gmap(lq, j)];
+                if constexpr (CLAMP) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j)
+                        if (clamp_holds(rset, (blk0 + bl) * 32 + gmap(lq, j))) rr[j] = 0.f;
+                }
                 // ---- 1. everything that needs the tiles: stage inputs (rk_common.py:62-66), error partial, copies
                 float ysI[8], asI[8], ysN[8], asN[8], y0c[8], a0c[8], k0y[8], k0a[8], ey[8], ea[8];
                 if (DO2) {
@@ -953,6 +968,12 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
                 const float dts = c.dtp[lb];
                 const InterpX ix = make_interp_x(xfin[lb]);
                 const bool okb = b < B;
+                int held = 0;   // bit j: this lane's trajectory holds gene j of the lane's four (q of it is 0)
+                if constexpr (CLAMP) {
+                    const ClampSet rset = clamp_set_row(clamp_gene, b, B, clamp_width);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) held |= clamp_holds(rset, gene0 + gmap(lq, 4 * s2 + j)) ? 1 << j : 0;
+                }
                 float y0v[4], a0v[4], ky[7][4], ka[7][4];
                 bload4(trs, lane32h, toff(C_Y0, ttl, bl), y0v);
                 bload4(trs, lane32h, toff(C_A0, ttl, bl), a0v);
@@ -1013,7 +1034,7 @@ __global__ __launch_bounds__(256) void k1_solve_adj3(Net net, D1 d, W1 w, SolveC
                     act_pair_fast_pk<2>(ys, an, ln);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        qn[j] = as[j] * rr[j];
+                        qn[j] = (CLAMP && (held >> j & 1)) ? 0.f : as[j] * rr[j];
                         // a (j - y) from k_y = -sgn relu(g) (j - y)
                         const float sgv = as[j] * (-sg * ky[S][j] * rinv[j]);
                         dgacc[j] += wl * sgv;

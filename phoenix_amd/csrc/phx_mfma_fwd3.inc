@@ -28,9 +28,13 @@ __host__ __device__ inline size_t ctlf3_bytes(int Bt, int ntg) { return ctl_byte
 // CALLS: the launch is d.TG independent odeint calls of d.Bcall rows under shared control (D1::Bcall, phx_solver.hpp):
 // batch group g is call g, it reads time row g when cfg.t_per_sample is set, and the rows of its last tile beyond
 // d.Bcall are padding (rowof).  A template flag, so that the instantiations of every other launch compile as before.
-// CLAMP (only with CALLS): call g holds the genes clamp_gene[g * clamp_width .. + clamp_width) (at most PHX_CLAMP_MAX) at
+// CLAMP with CALLS: call g holds the genes clamp_gene[g * clamp_width .. + clamp_width) (at most PHX_CLAMP_MAX) at
 // their initial values -- the sweeps read relu(g) of those genes as 0, so every stage slope of them is that of the model
 // with g = 0 on the set (phx_odeint_clamped_sets); an index no gene has clamps nothing and pads a set.
+// CLAMP without CALLS (phx_odeint_clamped_rows, per-trajectory control): the list is [B, clamp_width], one set per
+// trajectory ROW; a lane masks with the set of its own trajectory (clamp_set_row), read at the head of every tile visit
+// into four vector registers (the request flies under the wait for the hidden rows; the list, at most 16 bytes per row,
+// stays in the L2) -- not staged in LDS, whose budget the planner shares with the forms that have no list.
 // Without CLAMP the two trailing arguments are never read.
 template <int HT, int MAXT, bool HALF, bool SPLIT, bool CALLS = false, bool CLAMP = false>
 __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, SolveCfg cfg, const float *__restrict__ y0,
@@ -38,7 +42,6 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                                                       int *nfe_out, int *nsteps_out, const int *__restrict__ clamp_gene,
                                                       int clamp_width)
 {
-    static_assert(!CLAMP || CALLS, "a clamped gene belongs to a call");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lq = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: tile / row offsets stay scalar
@@ -51,7 +54,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
     auto rowof = [&](int lb) -> int { return CALLS ? (lb < d.Bcall ? grp * d.Bcall + lb : B) : grp * Bt + lb; };
     const int trow_sh = CALLS ? grp : 0;
     ClampSet cset{};   // the call's held genes
-    if constexpr (CLAMP) cset = clamp_set(clamp_gene, grp, clamp_width);
+    if constexpr (CLAMP && CALLS) cset = clamp_set(clamp_gene, grp, clamp_width);
     constexpr int F2 = 2 * HT;
     // small batches: the waves of a tile split its gene blocks (v3_split_parts, phx_mfma_v3common.inc)
     // (SPLIT is a template flag: the large-batch instantiation compiles exactly as without this path -- as run-time branches it cost
@@ -347,6 +350,8 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
             const int lb = ttl * 16 + li;
             const int b = rowof(lb);
             const int kb = __builtin_amdgcn_readfirstlane(kbs[ttl]);
+            ClampSet rset{};   // the held genes of the lane's trajectory row
+            if constexpr (CLAMP && !CALLS) rset = clamp_set_row(clamp_gene, b, B, clamp_width);
             const bool term = FOLD && (__builtin_amdgcn_readfirstlane(termf[ttl]) & 1);
             float ty0[8], tk[NKL][8];
             auto issue = [&](int bl) {
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(MAXT) void k1_solve_fwd3(Net net, D1 d, W1 w, Solve
                 if constexpr (CLAMP) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j)
-                        if (clamp_holds(cset, (blk0 + bl) * 32 + gmap(lq, j))) rr[j] = 0.f;
+                        if (clamp_holds(CALLS ? cset : rset, (blk0 + bl) * 32 + gmap(lq, j))) rr[j] = 0.f;
                 }
 #ifdef PHX_PROF_BLOCKS
                 if (tm.on && prof_sweep) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tm.mark(12); }   // diagnostic: tile wait

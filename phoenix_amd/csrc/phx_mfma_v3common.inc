@@ -29,6 +29,16 @@ __device__ __forceinline__ ClampSet clamp_set(const int *__restrict__ list, int 
         s.g[i] = i < width ? __builtin_amdgcn_readfirstlane(list[(long long)grp * width + i]) : -1;
     return s;
 }
+// The held genes of one trajectory ROW (the CLAMP forms without CALLS, and k1_solve_adj3's): row `b` of the [B, width]
+// list, one set per lane (the lane's trajectory), in vector registers.  A padding row (b >= B) reads nothing and holds
+// nothing.
+__device__ __forceinline__ ClampSet clamp_set_row(const int *__restrict__ list, int b, int B, int width)
+{
+    ClampSet s;
+#pragma unroll
+    for (int i = 0; i < PHX_CLAMP_MAX; ++i) s.g[i] = (i < width && b < B) ? list[(long long)b * width + i] : -1;
+    return s;
+}
 __device__ __forceinline__ bool clamp_holds(const ClampSet &s, int gene)
 {
     bool hit = false;

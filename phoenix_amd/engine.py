@@ -569,10 +569,82 @@ def solve_forward_clamped(p, y0, t64, clamp, rtol, atol, t_is_f32, max_num_steps
     return sol, stats[0], stats[1], stats[2]
 
 
+def clamped_rows_plan_exists(op, N, H, B, T, method="dopri5"):
+    """whether the per-row clamp kernels serve a batch of B rows in direction `op` (_lib.OP_ODEINT / OP_ADJOINT): dopri5
+    with H <= 48 where k1_solve_fwd3 / k1_solve_adj3 plan the shape (phx_odeint_clamped_rows_workspace_bytes, 0: not
+    served; any other method: not served); the size is remembered per shape and plan-switch setting"""
+    if method != "dopri5":
+        return 0
+    return _ws_size(("clamped_rows", op, N, H, B, T) + _plan_env(), "phx_odeint_clamped_rows_workspace_bytes", op, N, H, B, T)
+
+
+def _check_row_clamp(name, clamp, B, device):
+    if (clamp.dim() != 2 or clamp.shape[0] != B or not 1 <= clamp.shape[1] <= CLAMP_MAX or clamp.dtype != torch.int32 or
+            clamp.device != device or not clamp.is_contiguous()):
+        raise ValueError("%s: clamp must be a contiguous int32 tensor [B = %d, 1 .. %d] on the solve's device"
+                         % (name, B, CLAMP_MAX))
+
+
+def solve_forward_clamped_rows(p, y0, t64, clamp, rtol, atol, t_per_sample, t_is_f32, max_num_steps=0, stats=None):
+    """`solve_forward` for dopri5 under per-trajectory control where row b holds the genes clamp[b] (int32 device tensor
+    [B, width <= CLAMP_MAX], -1: padding; an all -1 row is an unperturbed sample) at their initial values
+    (phx_odeint_clamped_rows).  ValueError where `clamped_rows_plan_exists` is 0."""
+    B, N = y0.shape
+    _check_row_clamp("solve_forward_clamped_rows", clamp, B, y0.device)
+    T = t64.shape[-1]
+    nb = clamped_rows_plan_exists(_lib.OP_ODEINT, p.N, p.H, B, T)
+    if nb == 0:
+        raise ValueError("no kernel holds genes per row for N=%d, H=%d, B=%d" % (N, p.H, B))
+    sol = torch.empty((T, B, N), dtype=torch.float32, device=y0.device)
+    if stats is None:
+        stats = torch.empty((3, B), dtype=torch.int32, device=y0.device)
+    p.on_current_stream()
+    ws = _stream_buffer(_lib.OP_ODEINT, nb, y0.device, grow=1.25, solve=True)      # the stream's forward solve workspace
+    pkey = ("clamped_rows", p.N, p.H, B, T, int(t_per_sample)) + _plan_env()
+
+    def call(keep):
+        o = _opts("dopri5", _lib.CTRL_PER_TRAJECTORY, rtol, atol, t_per_sample, t_is_f32, max_num_steps, 1, keep)
+        return _lib.load().phx_odeint_clamped_rows(C.byref(p.c), _p(y0), _p(t64), B, T, C.byref(o), _p(clamp),
+                                                   clamp.shape[1], _p(sol), _p(stats[0]), _p(stats[1]), _p(stats[2]),
+                                                   _p(ws), nb, _stream_ptr())
+
+    _solve_call(_lib.OP_ODEINT, pkey, y0.device, call)
+    return sol, stats[0], stats[1], stats[2]
+
+
+def solve_adjoint_clamped_rows(p, t64, y_saved, grad_y, clamp, rtol, atol, t_per_sample, t_is_f32, want_grads=True,
+                               max_num_steps=0, stats=None):
+    """`solve_adjoint` for dopri5 under per-trajectory control of the per-row model of `solve_forward_clamped_rows`:
+    the continuous adjoint of row b is that of the model with g zeroed on clamp[b]
+    (phx_odeint_adjoint_backward_clamped_rows).  ValueError where `clamped_rows_plan_exists` is 0."""
+    T, B, N = y_saved.shape
+    _check_row_clamp("solve_adjoint_clamped_rows", clamp, B, y_saved.device)
+    nb = clamped_rows_plan_exists(_lib.OP_ADJOINT, p.N, p.H, B, T)
+    if nb == 0:
+        raise ValueError("no backward kernel holds genes per row for N=%d, H=%d, B=%d" % (N, p.H, B))
+    adj = torch.empty((B, N), dtype=torch.float32, device=y_saved.device)
+    if stats is None:
+        stats = torch.empty((3, B), dtype=torch.int32, device=y_saved.device)
+    grads = p.new_grads() if want_grads else None
+    p.on_current_stream()
+    ws = _stream_buffer(_lib.OP_ADJOINT, nb, y_saved.device, grow=1.25, solve=True)
+    pkey = ("clamped_rows", p.N, p.H, B, T, int(t_per_sample), bool(want_grads)) + _plan_env()
+
+    def call(keep):
+        o = _opts("dopri5", _lib.CTRL_PER_TRAJECTORY, rtol, atol, t_per_sample, t_is_f32, max_num_steps, 1, keep)
+        return _lib.load().phx_odeint_adjoint_backward_clamped_rows(
+            C.byref(p.c), _p(t64), B, T, C.byref(o), _p(clamp), clamp.shape[1], _p(y_saved), _p(grad_y), _p(adj),
+            C.byref(grads.c) if grads else None, _p(stats[0]), _p(stats[1]), _p(stats[2]), _p(ws), nb, _stream_ptr())
+
+    _solve_call(_lib.OP_ADJOINT, pkey, y_saved.device, call)
+    return adj, grads, stats[0], stats[1], stats[2]
+
+
 def solve_adjoint(p, t64, y_saved, grad_y, method, control, rtol, atol, t_per_sample, t_is_f32, want_grads=True,
-                  max_num_steps=0, stats=None, step_size=0.0):
+                  max_num_steps=0, stats=None, step_size=0.0, grads=None):
     """y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps.  `stats`: an int32 [3,B] to use (rows contiguous).
-    step_size > 0 (fixed-grid methods): the backward solve's own step, phx_odeint_adjoint_backward_stepped."""
+    step_size > 0 (fixed-grid methods): the backward solve's own step, phx_odeint_adjoint_backward_stepped.
+    grads: a Grads to write into under its own overwrite flag (`grads.c.overwrite` = 0 adds) instead of a new one."""
     T, B, N = y_saved.shape
     step = _step_of(method, step_size)
     if step and not max_num_steps:
@@ -580,7 +652,8 @@ def solve_adjoint(p, t64, y_saved, grad_y, method, control, rtol, atol, t_per_sa
     adj = torch.empty((B, N), dtype=torch.float32, device=y_saved.device)
     if stats is None:
         stats = torch.empty((3, B), dtype=torch.int32, device=y_saved.device)
-    grads = p.new_grads() if want_grads else None
+    if grads is None:
+        grads = p.new_grads() if want_grads else None
     p.on_current_stream()
     ws, nb = _workspace(_lib.OP_ADJOINT, p.N, p.H, B, T, y_saved.device)
     pkey = (p.N, p.H, B, T, method, control, int(t_per_sample), bool(want_grads), step) + _plan_env()
@@ -606,10 +679,10 @@ def _workspace_backprop(N, H, B, T, K, device):
 
 
 def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_f32, want_grads=True, max_num_steps=0,
-                   stats=None, step_size=0.0, grid_steps=0):
+                   stats=None, step_size=0.0, grid_steps=0, grads=None):
     """backpropagation through the fixed-grid steps of the forward solve (phx_odeint_backprop_backward):
     y_saved, grad_y [T,B,N] -> adj_y0 [B,N], Grads, status, nfe, nsteps, like solve_adjoint.  `grid_steps`: what
-    require_backprop returned for this call (the checkpoints of a step size)."""
+    require_backprop returned for this call (the checkpoints of a step size).  grads: as in solve_adjoint."""
     T, B, N = y_saved.shape
     step = _step_of(method, step_size)
     if step and not max_num_steps:
@@ -617,7 +690,8 @@ def solve_backprop(p, t64, y_saved, grad_y, method, control, t_per_sample, t_is_
     adj = torch.empty((B, N), dtype=torch.float32, device=y_saved.device)
     if stats is None:
         stats = torch.empty((3, B), dtype=torch.int32, device=y_saved.device)
-    grads = p.new_grads() if want_grads else None
+    if grads is None:
+        grads = p.new_grads() if want_grads else None
     p.on_current_stream()
     K = int(grid_steps) if step else 0
     ws, nb = _workspace_backprop(p.N, p.H, B, T, K, y_saved.device)

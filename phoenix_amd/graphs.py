@@ -19,6 +19,8 @@ the layout kernel): an optimizer stepped eagerly between two replays is seen by 
 
 The step function must be replay-safe in PyTorch's sense (static input tensors, no host reads, no data-dependent Python
 control flow).  Gradient all-reduces (phoenix_amd.parallel) are not recorded: one process, one device.
+A step whose solve holds genes per trajectory row (`odeint_adjoint(..., clamp=...)`) is not captured: its list is built on
+the host and copied to the device in every call.
 """
 import torch
 

@@ -118,14 +118,171 @@ def _out_shape(sol, y0, per_sample):
     return sol.reshape((sol.shape[0],) + tuple(y0.shape))
 
 
+class _RowClamp:
+    """The held sets of one odeint / odeint_adjoint call, one per trajectory row: `sets` (B sorted tuples, at least one
+    of them non-empty), the rows grouped by identical set in sorted order of the sets (the grouped path solves them in
+    this order), and -- set by the forward solve where the per-row kernels serve the call -- the device list they read."""
+
+    def __init__(self, sets):
+        self.sets = sets
+        groups = {}
+        for b, s in enumerate(sets):
+            groups.setdefault(s, []).append(b)
+        self.groups = sorted(groups.items())
+        self.dev = None          # int32 [B, width], shorter sets padded with -1: the kernel path
+        self.bp_steps = []       # grouped path, backpropagation through the steps: require_backprop's answer per group
+
+    def device_list(self, device):
+        width = max(1, max(len(s) for s in self.sets))
+        return torch.tensor([list(s) + [-1] * (width - len(s)) for s in self.sets], dtype=torch.int32).to(device)
+
+
+def _row_clamp(who, func, y0, t, options, clamp):
+    """`clamp` of odeint / odeint_adjoint / odeint_per_sample as a _RowClamp, or None where every set is empty (the call
+    then runs the unclamped entry points unchanged).  `_clamp_list`'s checks with one entry per trajectory row, on the
+    host, before anything is launched or asked of the device."""
+    if clamp is None:
+        return None
+    N = params_of(func)[0].shape[1]
+    if y0.shape[-1] != N:
+        raise ValueError("phoenix_amd: y0 last dimension %d != number of genes %d" % (y0.shape[-1], N))
+    sets = _clamp_list(clamp, y0.numel() // N, N, who=who, unit="row")
+    if not any(sets):
+        return None
+    ctl = options.get("batch_control", "per_trajectory" if t.ndimension() == 2 else "shared")
+    if ctl != "per_trajectory":
+        raise ValueError("%s: a clamp per trajectory row needs per-trajectory step control (t [B, T], or options="
+                         "{'batch_control': 'per_trajectory'}); under one shared controller per call use "
+                         "odeint_calls(..., clamp=...), whose clamp is per call" % who)
+    return _RowClamp(sets)
+
+
+def _group_params(params, held):
+    """engine parameters of the model a row with the held set `held` is defined by: g zeroed on the set, in a clone --
+    the caller's module is never modified"""
+    if not held:
+        return engine.params_cached(*params)
+    ws, bs, wp, bp, wa, g = params
+    gk = g.detach().clone()
+    gk.reshape(-1)[list(held)] = 0.0
+    return engine.Params(ws, bs, wp, bp, wa, gk)
+
+
+def _rows_of(rows, t64, per_sample, device):
+    idx = torch.tensor(rows, dtype=torch.long, device=device)
+    return idx, (t64.index_select(0, idx) if per_sample else t64)
+
+
+def _clamped_rows_forward(params, y2, t64, cfg, clamp, adjoint, stats=None):
+    """forward solve of a per-row clamped call -> sol [T,B,N], status (None: already checked), nfe, nsteps, Params (None
+    on the grouped path).  One launch of the per-row kernels (engine.solve_forward_clamped_rows) where they serve the
+    call -- and, with `adjoint`, its backward solve too --; else the grouped path: the rows of every distinct set, in
+    sorted order of the sets, through the ordinary entry points on `_group_params`, status checked per group."""
+    (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, _defer, steps) = cfg
+    N, H, B, T = params[0].shape[1], params[0].shape[0], y2.shape[0], t64.shape[-1]
+    backprop = adjoint and adj[3] and adj[0] in _FIXED_GRID_METHODS
+    y2 = y2.detach().contiguous()
+    if (engine.clamped_rows_plan_exists(_lib.OP_ODEINT, N, H, B, T, method) and
+            (not adjoint or engine.clamped_rows_plan_exists(_lib.OP_ADJOINT, N, H, B, T, adj[0]))):
+        p = engine.params_cached(*params)
+        clamp.dev = clamp.device_list(y2.device)
+        sol, status, nfe, nsteps = engine.solve_forward_clamped_rows(p, y2, t64, clamp.dev, rtol, atol, per_sample,
+                                                                     t_is_f32, max_steps, stats=stats)
+        return sol, status, nfe, nsteps, p
+    sol = torch.empty((T, B, N), dtype=torch.float32, device=y2.device)
+    nfe = torch.empty(B, dtype=torch.int32, device=y2.device)
+    nsteps = torch.empty(B, dtype=torch.int32, device=y2.device)
+    clamp.bp_steps = []
+    for held, rows in clamp.groups:
+        idx, tg = _rows_of(rows, t64, per_sample, y2.device)
+        p = _group_params(params, held)
+        if backprop:      # refused here, at the call, like the unclamped solve
+            clamp.bp_steps.append(engine.require_backprop(N, H, len(rows), T, method, tg, steps[0]))
+        if steps[0] or (adjoint and steps[1]):
+            if steps[0]:
+                engine.require_stepped_kernels(p, len(rows), T, method, backward=False)
+            if adjoint and steps[1] and not backprop:
+                engine.require_stepped_kernels(p, len(rows), T, adj[0], forward=False)
+        one, status, nf, ns = engine.solve_forward(p, y2.index_select(0, idx), tg, method, control, rtol, atol, per_sample,
+                                                   t_is_f32, max_steps, step_size=steps[0])
+        engine.raise_for_status(status)
+        sol[:, idx] = one
+        nfe[idx] = nf
+        nsteps[idx] = ns
+    return sol, None, nfe, nsteps, None
+
+
+def _clamped_rows_backward(params, t64, sol, grad_sol, cfg, clamp, p, need_p, stats=None):
+    """backward solve of a per-row clamped call -> adj_y0 [B,N], Grads or None, status (None: checked per group).  The
+    kernel path where the forward took it (clamp.dev); else group by group in the forward's order, the parameter
+    gradients accumulated into ONE Grads in that order and adj_y0 scattered back to the caller's rows."""
+    (method, control, _rtol, _atol, per_sample, t_is_f32, max_steps, adj, _defer, steps) = cfg
+    a_method, a_rtol, a_atol, via_odeint = adj
+    grad_sol = grad_sol.contiguous()
+    if clamp.dev is not None:
+        adj_y0, grads, status, _nfe, _ns = engine.solve_adjoint_clamped_rows(
+            p, t64, sol, grad_sol, clamp.dev, a_rtol, a_atol, per_sample, t_is_f32, want_grads=need_p,
+            max_num_steps=max_steps, stats=stats)
+        return adj_y0, grads, status
+    T, B, N = sol.shape
+    adj_y0 = torch.empty((B, N), dtype=torch.float32, device=sol.device)
+    grads = None
+    for i, (held, rows) in enumerate(clamp.groups):
+        idx, tg = _rows_of(rows, t64, per_sample, sol.device)
+        pg = _group_params(params, held)
+        if need_p and grads is None:
+            grads = pg.new_grads()      # the first group writes it (overwrite), the later ones add
+        ys, gs = sol.index_select(1, idx), grad_sol.index_select(1, idx)
+        if via_odeint and a_method in _FIXED_GRID_METHODS:
+            a, _g, status, _nfe, _ns = engine.solve_backprop(
+                pg, tg, ys, gs, method, control, per_sample, t_is_f32, want_grads=need_p, max_num_steps=max_steps,
+                step_size=steps[0], grid_steps=clamp.bp_steps[i], grads=grads)
+        else:
+            a, _g, status, _nfe, _ns = engine.solve_adjoint(
+                pg, tg, ys, gs, a_method, control, a_rtol, a_atol, per_sample, t_is_f32, want_grads=need_p,
+                max_num_steps=max_steps, step_size=steps[1], grads=grads)
+        engine.raise_for_status(status)
+        if grads is not None:
+            grads.c.overwrite = 0
+        adj_y0[idx] = a
+    return adj_y0, grads, None
+
+
+def _queue_status(stats):
+    """the status read-back of a training step, raised from loss.backward() (see _OdeintAdjointFn.backward)"""
+    if engine.status_mode() == "deferred":
+        engine.defer_status(stats)      # checked at a later engine call, once the kernel has finished
+    else:
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(lambda: engine.raise_for_status(stats))
+        except Exception:   # noqa: BLE001  (no running graph task: check right here)
+            engine.raise_for_status(stats)
+
+
 class _OdeintAdjointFn(torch.autograd.Function):
     """OdeintAdjointMethod (adjoint.py:9-162): forward = no-grad solve, saves (t, y, params);
-    backward = reverse-time augmented solve on the engine."""
+    backward = reverse-time augmented solve on the engine.  clamp: a _RowClamp (held genes per trajectory row), carried
+    from forward to backward with its device list."""
 
     @staticmethod
-    def forward(ctx, y2, t64, cfg, ws, bs, wp, bp, wa, g):
+    def forward(ctx, y2, t64, cfg, ws, bs, wp, bp, wa, g, clamp=None):
         (method, control, rtol, atol, per_sample, t_is_f32, max_steps, adj, defer, steps) = cfg
         engine.check_pending_status()
+        ctx.phx_clamp = clamp
+        if clamp is not None:
+            stats = torch.empty((3, 2 if defer else 1, y2.shape[0]), dtype=torch.int32, device=y2.device)
+            ctx.set_materialize_grads(False)
+            sol, status, nfe, _ns, p = _clamped_rows_forward((ws, bs, wp, bp, wa, g), y2, t64, cfg, clamp, True, stats[:, 0])
+            # (the grouped path has checked every group; the kernel path defers like the unclamped solve below)
+            ctx.phx_stats = stats if defer and status is not None else None
+            if status is not None and not defer:
+                engine.raise_for_status(status)
+            ctx.cfg = cfg
+            ctx.phx_params = p
+            ctx.phx_versions = tuple(x._version for x in (ws, bs, wp, bp, wa, g))
+            ctx.save_for_backward(t64, sol, ws, bs, wp, bp, wa, g)
+            ctx.mark_non_differentiable(nfe)
+            return sol, nfe
         # odeint(method=<fixed grid>) whose backward pass backpropagates through the steps: every shape that pass would
         # refuse is refused HERE, at the call, before anything is launched (H > 128, PHX_ENGINE=v0, a grid whose
         # checkpoints exceed engine.BACKPROP_MAX_CHECKPOINT_BYTES)
@@ -173,8 +330,15 @@ class _OdeintAdjointFn(torch.autograd.Function):
         p = ctx.phx_params
         if ctx.phx_versions != tuple(x._version for x in (ws, bs, wp, bp, wa, g)):
             p = engine.params_cached(ws, bs, wp, bp, wa, g)   # parameters were modified in place since forward
-        need_p = any(ctx.needs_input_grad[3:])
+        need_p = any(ctx.needs_input_grad[3:9])
         bstats = None if ctx.phx_stats is None else ctx.phx_stats[:, 1]
+        if ctx.phx_clamp is not None:
+            adj_y0, grads, status = _clamped_rows_backward((ws, bs, wp, bp, wa, g), t64, sol, grad_sol, ctx.cfg,
+                                                           ctx.phx_clamp, p, need_p, bstats)
+            if status is not None:      # the kernel path: one read-back for both launches, as below
+                _queue_status(status if ctx.phx_stats is None else ctx.phx_stats[0])
+            gp = grads.as_reference_layout(g.shape) if need_p else (None,) * 6
+            return (adj_y0, None, None) + tuple(gp) + (None,)
         if via_odeint and a_method in _FIXED_GRID_METHODS:
             # the reference's `odeint`: backpropagation through the solver's own steps (the discrete adjoint), not the
             # continuous adjoint below, from which it differs at O(1) for one unconverged step per interval
@@ -189,22 +353,15 @@ class _OdeintAdjointFn(torch.autograd.Function):
         # end-of-backward callback of the autograd engine (the mechanism DDP finalises with): the exception still comes
         # out of loss.backward(), but the host returns the gradients and runs its accumulation nodes while the kernel
         # is still executing instead of after it.
-        stats = status if ctx.phx_stats is None else ctx.phx_stats[0]          # [2, B]: forward and backward status
-        if engine.status_mode() == "deferred":
-            engine.defer_status(stats)      # checked at a later engine call, once the kernel has finished
-        else:
-            try:
-                torch.autograd.Variable._execution_engine.queue_callback(lambda: engine.raise_for_status(stats))
-            except Exception:   # noqa: BLE001  (no running graph task: check right here)
-                engine.raise_for_status(stats)
+        _queue_status(status if ctx.phx_stats is None else ctx.phx_stats[0])    # [2, B]: forward and backward status
         if need_p:
             gws, gbs, gwp, gbp, gwa, gg = grads.as_reference_layout(g.shape)
         else:
             gws = gbs = gwp = gbp = gwa = gg = None
-        return adj_y0, None, None, gws, gbs, gwp, gbp, gwa, gg
+        return adj_y0, None, None, gws, gbs, gwp, gbp, gwa, gg, None
 
 
-def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_stats=False):
+def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_stats=False, clamp=None):
     """odeint.py:30-74.  The reference's `odeint` returns an autograd-tracked solution (backpropagation through the
     solver's own operations).  For an ODENet:
       * nothing requires grad, autograd is off (validation, analysis callers), or `return_stats`: plain forward solve
@@ -220,16 +377,30 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
         (max_num_steps exceeded) are then raised with the backward's, from backward(), as for `odeint_adjoint`;
       * something requires grad, dopri5: the call is routed through `odeint_adjoint`; the continuous adjoint agrees with
         backpropagation through the converged solve to the solver tolerance (<= 2e-6 relative).
-    Gradients with respect to `t` are not computed."""
+    Gradients with respect to `t` are not computed.
+    clamp (one entry per trajectory ROW of y0; None: no gene is held): see `odeint_adjoint`.  Note that `odeint_calls`'
+    clamp is per CALL (one shared controller, forward only); this one is per row and differentiable."""
     y0, t, rtol, atol, method, options = _check_inputs(func, y0, t, rtol, atol, method, options)
     if not _is_odenet(func):      # any other module: unfused torch stepper, differentiable by plain backpropagation
+        if clamp is not None:
+            raise NotImplementedError("phoenix_amd: odeint: clamp needs a PHOENIX ODENet")
         engine._require_gpu(y0, "y0")          # like every other entry point: no CPU compute path in this package
         assert t.ndimension() == 1 and not return_stats, "per-sample grids / solver statistics need a PHOENIX ODENet"
         return generic.odeint(func, y0, t, rtol, atol, method, options)
     if not return_stats and torch.is_grad_enabled() and (y0.requires_grad or any(x.requires_grad for x in params_of(func))):
-        return odeint_adjoint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options, _via_odeint=True)
+        return odeint_adjoint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options, _via_odeint=True,
+                              clamp=clamp, _who="odeint")
+    held = _row_clamp("odeint", func, y0, t, options, clamp)
     params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t, options)
     engine.check_pending_status()
+    if held is not None:
+        cfg = (method, control, rtol, atol, per_sample, t_is_f32, int(options.get("max_num_steps", 0)), None, False,
+               (options.get("step_size", 0.0), 0.0))
+        sol, status, nfe, nsteps, _p = _clamped_rows_forward(params, y2, t64, cfg, held, False)
+        if status is not None:
+            engine.raise_for_status(status)
+        out = _out_shape(sol, y0, per_sample)
+        return (out, nfe, nsteps) if return_stats else out
     p = engine.params_cached(*params)
     sol, status, nfe, nsteps = engine.solve_forward(p, y2.detach().contiguous(), t64, method, control, rtol, atol,
                                                     per_sample, t_is_f32, int(options.get("max_num_steps", 0)),
@@ -242,19 +413,21 @@ def odeint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, return_
 _INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
 
 
-def _clamp_list(clamp, K, N):
+def _clamp_list(clamp, K, N, who="odeint_calls", unit="call"):
     """`clamp` of odeint_calls as K sorted tuples of distinct genes in [0, N) -- the set each call holds, () for none --
     checked on the host before anything is launched.  Per call an int (-1: none) or a sequence of at most
-    engine.CLAMP_MAX ints, or for all calls a 1-D / 2-D integer tensor, -1 entries being padding."""
+    engine.CLAMP_MAX ints, or for all calls a 1-D / 2-D integer tensor, -1 entries being padding.
+    who, unit: the caller and what an entry belongs to, for the messages (odeint / odeint_adjoint / odeint_per_sample
+    hold a set per trajectory ROW: the same checks with K = the rows)."""
     if torch.is_tensor(clamp):
         if clamp.dim() not in (1, 2) or clamp.dtype not in _INT_DTYPES:
-            raise TypeError("odeint_calls: clamp must be a 1-D or 2-D integer tensor or a sequence of ints / int sequences, "
-                            "got %s %s" % (clamp.dtype, tuple(clamp.shape)))
+            raise TypeError("%s: clamp must be a 1-D or 2-D integer tensor or a sequence of ints / int sequences, "
+                            "got %s %s" % (who, clamp.dtype, tuple(clamp.shape)))
         clamp = clamp.tolist()
     try:
         clamp = list(clamp)
     except TypeError:
-        raise TypeError("odeint_calls: clamp must be a sequence of %d ints or int sequences" % K) from None
+        raise TypeError("%s: clamp must be a sequence of %d ints or int sequences" % (who, K)) from None
     sets = []
     for entry in clamp:
         if hasattr(entry, "tolist"):      # numpy and tensor scalars / rows
@@ -262,17 +435,17 @@ def _clamp_list(clamp, K, N):
         genes = list(entry) if isinstance(entry, (list, tuple, range, set, frozenset)) else [entry]
         for g in genes:
             if isinstance(g, bool) or not hasattr(g, "__index__"):
-                raise TypeError("odeint_calls: clamp entries must be integers, got %r" % (g,))
+                raise TypeError("%s: clamp entries must be integers, got %r" % (who, g))
         sets.append([int(g) for g in genes])
     if len(sets) != K:
-        raise ValueError("odeint_calls: clamp names genes for %d calls, there are %d" % (len(sets), K))
+        raise ValueError("%s: clamp names genes for %d %ss, there are %d" % (who, len(sets), unit, K))
     for genes in sets:
         for g in genes:
             if g < -1 or g >= N:
-                raise ValueError("odeint_calls: clamp entry %d is not a gene of 0 .. %d (or -1: none)" % (g, N - 1))
+                raise ValueError("%s: clamp entry %d is not a gene of 0 .. %d (or -1: none)" % (who, g, N - 1))
         if len(genes) > engine.CLAMP_MAX:
-            raise ValueError("odeint_calls: a clamp set of %d entries, a call holds at most %d genes"
-                             % (len(genes), engine.CLAMP_MAX))
+            raise ValueError("%s: a clamp set of %d entries, a %s holds at most %d genes"
+                             % (who, len(genes), unit, engine.CLAMP_MAX))
     return [tuple(sorted(set(g for g in genes if g >= 0))) for genes in sets]     # duplicates count once
 
 
@@ -401,8 +574,24 @@ def _adjoint_step(options, a_step, adjoint_method):
 
 
 def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint_rtol=None,
-                   adjoint_atol=None, adjoint_method=None, adjoint_options=None, adjoint_params=None, _via_odeint=False):
-    """adjoint.py:165-204.  Gradients flow to y0 and to the six ODENet parameters."""
+                   adjoint_atol=None, adjoint_method=None, adjoint_options=None, adjoint_params=None, _via_odeint=False,
+                   clamp=None, _who="odeint_adjoint"):
+    """adjoint.py:165-204.  Gradients flow to y0 and to the six ODENet parameters.
+    clamp (None: no gene is held): per trajectory ROW b of y0 [B,1,N] / [B,N] a set of at most engine.CLAMP_MAX genes
+    held at their initial values for the whole time course of that row -- perturbation time courses (knockouts at level
+    0, over-expression at a high level) to train on, mixed with unperturbed rows (the empty set) in one minibatch.  B
+    entries, each an int (-1: none) or a sequence of up to four ints, or an integer tensor [B] / [B, W <= 4] padded
+    with -1; checked on the host before any launch.  Row b IS the solve of the model whose gene_multipliers are 0 on
+    its set (odenet.py:85-91), forward and backward: d y[b, k] / dt = 0 on the set; the gradient is the continuous
+    adjoint of that per-row model -- y0.grad[b, k] is dL/d(the level gene k is held at), gene_multipliers.grad[k] and
+    row k of the combine layer's weight gradient receive nothing from row b; parameter gradients are summed over the
+    rows.  The module is never modified.  Per-trajectory step control only (t [B, T], or options={"batch_control":
+    "per_trajectory"}); with one shared controller a per-row clamp raises ValueError -- `odeint_calls`' clamp is per
+    CALL, this one per ROW.  dopri5 with H <= 48 runs the per-row forms of k1_solve_fwd3 / k1_solve_adj3, one launch
+    per direction; everything else (H > 48, euler / midpoint / rk4, step_size, PHX_ENGINE=v0) groups the rows by
+    identical set and runs every group through the ordinary entry points on a cloned multiplier vector zeroed on the
+    set, parameter gradients accumulated in the sorted order of the sets.  A list whose sets are all empty runs the
+    unclamped call unchanged."""
     # adjoint_options may hold step_size and nothing else; absent, the backward solve inherits the forward's step
     # (adjoint.py:182-183: adjoint_options defaults to options)
     adjoint_options = {} if adjoint_options is None else dict(adjoint_options)
@@ -413,6 +602,8 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     if a_step is not None:
         a_step = _step_size(a_step)
     if not _is_odenet(func):      # any other module: the reference's augmented system on the unfused torch stepper
+        if clamp is not None:
+            raise NotImplementedError("phoenix_amd: %s: clamp needs a PHOENIX ODENet" % _who)
         y0, t, rtol, atol, method, options = _check_inputs(func, y0, t, rtol, atol, method, options)
         engine._require_gpu(y0, "y0")          # like every other entry point: no CPU compute path in this package
         assert t.ndimension() == 1, "per-sample time grids need a PHOENIX ODENet"
@@ -434,6 +625,7 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
         raise NotImplementedError("phoenix_amd: adjoint_method '%s' not supported" % adjoint_method)
     if a_step is not None and adjoint_method not in _FIXED_GRID_METHODS:      # as options with dopri5 (misc.py:204-206)
         warnings.warn("phoenix_amd: Unexpected arguments {}".format({"step_size": a_step}))
+    held = _row_clamp(_who, func, y0, t, options, clamp)
     params, y2, t64, B, N, per_sample, t_is_f32, control = _prepare(func, y0, t, options)
     # The forward status is read together with the backward solve's only when a backward pass can come: autograd must
     # be recording AND something must require grad (needs_input_grad mirrors .requires_grad even under no_grad: the
@@ -445,14 +637,17 @@ def odeint_adjoint(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None,
     cfg = (method, control, rtol, atol, per_sample, t_is_f32, int(options.get("max_num_steps", 0)),
            (adjoint_method, float(adjoint_rtol), float(adjoint_atol), bool(_via_odeint)), defer,
            (options.get("step_size", 0.0), _adjoint_step(options, a_step, adjoint_method)))
-    sol, _nfe = _OdeintAdjointFn.apply(y2, t64, cfg, *params)
+    sol, _nfe = _OdeintAdjointFn.apply(y2, t64, cfg, *params, held)
     return _out_shape(sol, y0, per_sample)
 
 
-def odeint_per_sample(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint=True):
+def odeint_per_sample(func, y0, t, rtol=1e-7, atol=1e-9, method=None, options=None, adjoint=True, clamp=None):
     """The reference's per-sample python loop as ONE launch:
         for time, batch_point in zip(t, batch): odeint(odenet, batch_point, time, method)[1]
-    y0 [B,1,N] (or [B,N]), t [B,T]; returns [T, *y0.shape]; independent step control per sample."""
+    y0 [B,1,N] (or [B,N]), t [B,T]; returns [T, *y0.shape]; independent step control per sample.
+    clamp: the genes sample b holds for its whole time course, one entry per sample (`odeint_adjoint`)."""
     assert t.ndimension() == 2, "odeint_per_sample needs t of shape [B, T]"
-    fn = odeint_adjoint if adjoint else odeint
-    return fn(func, y0, t, rtol=rtol, atol=atol, method=method, options=options)
+    if adjoint:
+        return odeint_adjoint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options, clamp=clamp,
+                              _who="odeint_per_sample")
+    return odeint(func, y0, t, rtol=rtol, atol=atol, method=method, options=options, clamp=clamp)
