@@ -637,6 +637,42 @@ int phx_pathway_permutations(const float *scores, int N, const long long *ptr, c
                              unsigned long long seed, long long first, long long n_perm, double *base, long long *count,
                              double *s1, double *s2, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The reduced Jacobian of the steady-state solve (phoenix_amd.steady_states).  On the genes that move,
+ * f(y) = relu(g) (Wa h(y) - y) with h(y) = [Ws a(y) + bs ; exp(Wp l(y) + bp)]; with C(y) = [Ws diag(a'(y)) ;
+ * diag(v) Wp diag(l'(y))], v = exp(Wp l(y) + bp), a linearly implicit step of per-gene weights m is delta = m (r + Wa x),
+ * (I - S) x = w.  For the B states y [B, N] and weights m [B, N] (float, any values; exact 0 marks a gene that takes no
+ * part: its derivative and its residual are not read into any sum) the call writes, all float:
+ *   S   [B, 2H, 2H]   S_b = C(y_b) diag(m_b) Wa
+ *   w   [B, 2H]       w_b = C(y_b) (m_b r_b), where r [B, N] is given; r and w are both null or both given
+ *   hid [B, 2H]       (Ws a(y_b) + bs, exp(Wp l(y_b) + bp)), the hidden vector, over ALL genes
+ * phx_steady.hip: one contraction over the genes with the rows of Ws / Wp as A operands and the N x (2H + 2) block
+ * [diag(d m) WaT^T | act | d m r] as B operand, v_mfma_f32_16x16x4_f32.  A workgroup owns a 64 x 64 output block of one
+ * branch, a segment of the gene axis and four states; 32 genes of its weight rows at a time stay in LDS while it walks the
+ * states.  The gene axis is cut into S = min(ceil(N / 32), ceil(256 / blocks(H))) segments, a function of (N, H) alone; a
+ * second kernel adds the segments' partial blocks in segment order, adds the bias, takes exp and scales the product rows by
+ * v_j.  No atomics.  The bits of a state depend neither on B nor on the other states of the call.  More states than 64 MiB
+ * of partial blocks hold are walked in chunks inside the call.  Nothing allocates or synchronises.
+ * 1 <= H <= 256, N >= 1, B >= 1.  PHX_ERR_BAD_ARG before any device call: null p / Ws / bs / Wp / bp / WaT / y / m / S / hid,
+ * a shape outside those ranges, r without w or w without r.  PHX_ERR_WORKSPACE when workspace is null or workspace_bytes <
+ * phx_reduced_jacobian_workspace_bytes(N, H, B) (0 for a shape the call refuses). */
+size_t phx_reduced_jacobian_workspace_bytes(int N, int H, int B);
+int phx_reduced_jacobian(const phx_params *p, const float *y, const float *m, const float *r, int B, float *S, float *w,
+                         float *hid, void *workspace, size_t workspace_bytes, void *stream);
+/* The RHS-sized passes and the dense solve of that iteration, each in a sum order fixed by the shape alone, so that a
+ * state's bits do not depend on the batch it is solved in.  B <= 65535 for the first two.
+ * phx_steady_residual: hid [B, 2H] as above and r [B, N] = Wa hid - y (c ascending per gene).
+ * phx_steady_update:   out [B, N] = y + m (r + Wa x) where m != 0, y (to the bit) where m == 0; x [B, 2H].
+ * phx_steady_solve:    (I - S_b) x_b = w_b in double, LU with partial pivoting, one workgroup per state; x [B, 2H] float,
+ *   info [B] = 0, k + 1 where column k has no finite non-zero pivot, -1 where the solution is not finite (x_b = 0 then).
+ *   workspace: phx_steady_solve_workspace_bytes(H, B) = B (2H)^2 doubles.
+ * PHX_ERR_BAD_ARG before any device call for a null pointer or a shape outside the ranges, PHX_ERR_WORKSPACE as above. */
+int phx_steady_residual(const phx_params *p, const float *y, int B, float *hid, float *r, void *stream);
+int phx_steady_update(const phx_params *p, const float *y, const float *m, const float *r, const float *x, int B, float *out,
+                      void *stream);
+size_t phx_steady_solve_workspace_bytes(int H, int B);
+int phx_steady_solve(const float *S, const float *w, int H, int B, float *x, int *info, void *workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

@@ -21,5 +21,7 @@ from .analysis import (Edges, EpistasisPerPair, EpistasisRecovery, EpistasisReco
                        write_permutation_table)
 from .simulator import (HillJacobian, HillPattern, HillSystem, generate_dataset, jacobian_reference,  # noqa: F401
                         knockouts_reference, rates_reference)
+from .steady import (KnockoutSteadyStates, SteadyStates, knockout_steady_states, reduced_jacobian,  # noqa: F401
+                     steady_states, steady_states_reference)
 
 __version__ = "0.1.0"

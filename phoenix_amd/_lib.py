@@ -45,7 +45,9 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_knockout_epistasis_workspace_bytes", "phx_knockout_epistasis", "phx_debug_adj3_tail_words",
            "phx_hill_knockout_sets", "phx_effects_apply_workspace_bytes", "phx_effects_apply",
            "phx_odeint_clamped_rows_workspace_bytes", "phx_odeint_clamped_rows",
-           "phx_odeint_adjoint_backward_clamped_rows", "phx_debug_clamped_rows_plan")
+           "phx_odeint_adjoint_backward_clamped_rows", "phx_debug_clamped_rows_plan",
+           "phx_reduced_jacobian_workspace_bytes", "phx_reduced_jacobian", "phx_steady_residual", "phx_steady_update",
+           "phx_steady_solve_workspace_bytes", "phx_steady_solve")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -195,6 +197,16 @@ def load():
     lib.phx_knockout_epistasis_workspace_bytes.restype = C.c_size_t
     lib.phx_knockout_epistasis.argtypes = ([vp] * 3 + [C.c_int] * 5 + [C.POINTER(C.c_int)] * 3 + [vp] * 7 +
                                            [C.c_size_t, vp])
+    # (the same: an earlier build of ABI 7 has no steady-state unit)
+    if path == _build.LIB or hasattr(lib, "phx_reduced_jacobian"):
+        lib.phx_reduced_jacobian_workspace_bytes.argtypes = [C.c_int] * 3
+        lib.phx_reduced_jacobian_workspace_bytes.restype = C.c_size_t
+        lib.phx_reduced_jacobian.argtypes = [C.POINTER(PhxParams), vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
+        lib.phx_steady_residual.argtypes = [C.POINTER(PhxParams), vp, C.c_int, vp, vp, vp]
+        lib.phx_steady_update.argtypes = [C.POINTER(PhxParams), vp, vp, vp, vp, C.c_int, vp, vp]
+        lib.phx_steady_solve_workspace_bytes.argtypes = [C.c_int] * 2
+        lib.phx_steady_solve_workspace_bytes.restype = C.c_size_t
+        lib.phx_steady_solve.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

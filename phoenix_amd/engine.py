@@ -1411,3 +1411,65 @@ def network_score(params, mode, regulator, target, y=None, ph=None, orient=False
     ap = float((hits / P * (tp.to(torch.float64) / (tp + fp).to(torch.float64))).sum())
     threshold = torch.flip(u, (0,)).view(torch.float32)
     return auroc, ap, P, Nn, threshold, tp, fp
+
+
+OP_REDUCED_JACOBIAN = 15   # workspace-cache key of reduced_jacobian (phx_reduced_jacobian_workspace_bytes sizes it)
+OP_STEADY_SOLVE = 16       # ... and of steady_solve (phx_steady_solve_workspace_bytes)
+
+
+def _steady_rows(name, p, x, what="y"):
+    """`x` as contiguous float32 [B, N] rows on the parameters' device"""
+    _require_gpu(x, what)
+    if x.dim() != 2 or x.shape[1] != p.N or x.shape[0] < 1:
+        raise ValueError("%s: %s must be [B, %d], got %s" % (name, what, p.N, tuple(x.shape)))
+    return x.detach().contiguous()
+
+
+def reduced_jacobian(p, y, m, r=None):
+    """phx_reduced_jacobian on laid-out parameters (`Params`): for the states y [B, N] and the per-gene weights m [B, N]
+    (float32; exact 0: the gene takes no part) returns (S [B, 2H, 2H], w [B, 2H] or None, hid [B, 2H]) with
+    S_b = C(y_b) diag(m_b) Wa, w_b = C(y_b) (m_b r_b) where `r` [B, N] is given, and the hidden vector of y_b."""
+    y2 = _steady_rows("reduced_jacobian", p, y)
+    m2 = _steady_rows("reduced_jacobian", p, m, "m")
+    r2 = None if r is None else _steady_rows("reduced_jacobian", p, r, "r")
+    if m2.shape != y2.shape or (r2 is not None and r2.shape != y2.shape):
+        raise ValueError("reduced_jacobian: y, m and r must have one shape")
+    B, H2, dev = y2.shape[0], 2 * p.H, y2.device
+    S = torch.empty((B, H2, H2), dtype=torch.float32, device=dev)
+    hid = torch.empty((B, H2), dtype=torch.float32, device=dev)
+    w = None if r2 is None else torch.empty((B, H2), dtype=torch.float32, device=dev)
+    p.on_current_stream()
+    nbytes = _ws_size((OP_REDUCED_JACOBIAN, p.N, p.H, B), "phx_reduced_jacobian_workspace_bytes", p.N, p.H, B)
+    ws = _analysis_workspace(OP_REDUCED_JACOBIAN, nbytes, dev)
+    _check_call(_lib.load().phx_reduced_jacobian(C.byref(p.c), _p(y2), _p(m2), _p(r2), B, _p(S), _p(w), _p(hid), _p(ws), nbytes,
+                                                 _stream_ptr()))
+    return S, w, hid
+
+
+def steady_residual(p, y):
+    """(hid [B, 2H], r [B, N] = Wa hid - y) of the states y [B, N]: phx_steady_residual"""
+    y2 = _steady_rows("steady_residual", p, y)
+    hid = torch.empty((y2.shape[0], 2 * p.H), dtype=torch.float32, device=y2.device)
+    r = torch.empty_like(y2)
+    p.on_current_stream()
+    _check_call(_lib.load().phx_steady_residual(C.byref(p.c), _p(y2), y2.shape[0], _p(hid), _p(r), _stream_ptr()))
+    return hid, r
+
+
+def steady_update(p, y, m, r, x):
+    """y + m (r + Wa x) where m != 0, y where m == 0: phx_steady_update (all contiguous float32 on the device)"""
+    out = torch.empty_like(y)
+    p.on_current_stream()
+    _check_call(_lib.load().phx_steady_update(C.byref(p.c), _p(y), _p(m), _p(r), _p(x), y.shape[0], _p(out), _stream_ptr()))
+    return out
+
+
+def steady_solve(S, w):
+    """(x [B, n] float32, info [B] int32) of (I - S_b) x_b = w_b, solved in float64 on the device: phx_steady_solve"""
+    B, n = w.shape
+    x = torch.empty_like(w)
+    info = torch.empty(B, dtype=torch.int32, device=w.device)
+    nbytes = _ws_size((OP_STEADY_SOLVE, n, B), "phx_steady_solve_workspace_bytes", n // 2, B)
+    ws = _analysis_workspace(OP_STEADY_SOLVE, nbytes, w.device)
+    _check_call(_lib.load().phx_steady_solve(_p(S), _p(w), n // 2, B, _p(x), _p(info), _p(ws), nbytes, _stream_ptr()))
+    return x, info
