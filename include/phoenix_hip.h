@@ -407,6 +407,33 @@ int phx_hill_knockout_sets(const int *code, const int *off, const int *len, cons
                            const double *times, int T, double dt_max, const int *genes_host, const float *values_host,
                            int width, int K, float *out, int B, int N, void *stream);
 
+/* The steady states (attractors) of the simulator by implicit relaxation (additive, ABI 7; DESIGN.md section 8p,
+ * phx_hillss.hip): per row of x0 [R, N] the iteration (sigma I - J(x)) delta = f(x), sigma = 1 / tau (0 for tau = inf:
+ * Newton), x <- x + delta under the control of phoenix_amd.steady_states -- rho = max |f| over the moving genes; done at
+ * rho <= tol (compared in float); a step is accepted iff the new rho' is finite and <= 2 rho, then tau <- tau min(10, max(2,
+ * rho / rho')), else x stays and tau <- tau / 4.  f are the rates of phx_hill_rhs, J their Jacobian on the pattern (eptr,
+ * ereg, E) of phx_hill_jacobian, by the same interpreter rules.  The schedule, device int32: order [N] lists the genes by
+ * strongly connected component of the pattern without its diagonal, the components by level (1 + the highest level of a
+ * component that regulates it); comp_ptr [n_comp + 1] cuts order into components, level_ptr [n_level + 1] the components into
+ * levels; largest is the size of the largest component.  A step is a forward substitution over the levels: a one-gene
+ * component is delta_j = (f_j + sum_{k != j} J_jk delta_k) / (sigma - J_jj) in float, the row's entries ascending; a larger one
+ * solves its block in double by LU with partial pivoting.  A gene with an empty program or moving[r, n] == 0 (moving: uint8
+ * [R, N], NULL: every gene with a program moves) has f = 0 and delta = 0 and keeps its x0 bits.
+ * One launch, one workgroup per row, no atomics; the bits of a row do not depend on R or on the other rows.
+ * Outputs: x [R, N]; residual [R] = rho at x; iterations [R] = the steps tried; status [R] = 0 converged, 1 max_iter reached,
+ * 2 a zero or non-finite pivot or divisor (x is the last accepted state); tau [R].
+ * phx_hill_steady_lds_bytes: the LDS of a workgroup, 0 for a system the call refuses (largest > PHX_HILL_SCC_MAX or more
+ * than 64 KiB: (largest^2 + largest) doubles for largest > 1, and 5 N + E + 6 words).
+ * PHX_ERR_BAD_ARG before any launch: such a system, a null pointer other than moving, R < 1, N < 1, E < 0, max_iter < 0,
+ * n_comp outside 1 .. N, n_level outside 1 .. n_comp, tol not finite or < 0, tau0 not > 0. */
+#define PHX_HILL_SCC_MAX 64
+size_t phx_hill_steady_lds_bytes(int N, long long E, int largest);
+int phx_hill_steady(const int *code, const int *off, const int *len, const float *consts, const long long *eptr,
+                    const int *ereg, long long E, const int *order, const int *comp_ptr, int n_comp, const int *level_ptr,
+                    int n_level, int largest, const float *x0, const unsigned char *moving, int R, int N, double tol,
+                    int max_iter, double tau0, float *x, float *residual, int *iterations, int *status, float *tau,
+                    void *stream);
+
 /* the scoring tail of the gene-influence scan (find_gene_influences.py:64-77) on the solver's
  * own output.  sol [T, 2 * pairs * B, N] is the block phx_odeint wrote for 2 * pairs calls of B rows (opts->calls): call
  * 2j is the unperturbed solve of pair j, call 2j + 1 the perturbed one; genes_host [pairs] (HOST) names the perturbed

@@ -18,9 +18,9 @@ from .analysis import (Edges, EpistasisPerPair, EpistasisRecovery, EpistasisReco
                        network_score,
                        Propagation, effects_apply, network_propagation, propagation_reference,
                        pathway_permutation_test, read_network, read_pathways, recovery_scores, write_link_list,
-                       write_permutation_table)
-from .simulator import (HillJacobian, HillPattern, HillSystem, generate_dataset, jacobian_reference,  # noqa: F401
-                        knockouts_reference, rates_reference)
+                       write_permutation_table, SteadyStateRecovery, steady_state_recovery, steady_state_recovery_scores)
+from .simulator import (HillBlocks, HillJacobian, HillPattern, HillSystem, block_substitution,  # noqa: F401
+                        generate_dataset, jacobian_reference, knockouts_reference, rates_reference)
 from .steady import (KnockoutSteadyStates, SteadyStates, knockout_steady_states, reduced_jacobian,  # noqa: F401
                      steady_states, steady_states_reference)
 

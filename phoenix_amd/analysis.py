@@ -863,6 +863,75 @@ def epistasis_recovery(odenet, system, y0, genes=None, pairs=None, value=0.0, ti
                              _pearson(_average_ranks(a), _average_ranks(b)), true, learned)
 
 
+# ------------------------------------------------------------------ recovery of the simulator's attractors
+SteadyStateRecovery = collections.namedtuple("SteadyStateRecovery", ("genes", "n_entries", "sign_agreement", "pearson", "spearman",
+                                                                     "slope", "per_gene", "base_pearson", "base_rms",
+                                                                     "scores_spearman", "n_unconverged", "true", "learned"))
+
+
+def steady_state_recovery_scores(genes, true, learned, regulated=None, min_effect=0.0):
+    """The statistics of `steady_state_recovery` from the two screens' results, on the host in float64.  true / learned:
+    `KnockoutSteadyStates` (or anything with their fields; tensors or arrays) of the same K genes over the same B states.
+    A row -- an unperturbed state b, or a knockout row k B + b -- counts iff its status is 0 on BOTH sides; shift and
+    magnitude [K, N] are the means over the counted rows of each knockout (NaN for a knockout without one, which
+    `knockout_recovery_scores` then leaves out: |NaN| > min_effect is false).  regulated: bool [N], the genes the states are
+    compared on (default all).  Returns SteadyStateRecovery(genes, n_entries, sign_agreement, pearson, spearman, slope,
+    per_gene -- `knockout_recovery_scores` of the two shift matrices --, base_pearson, base_rms -- the Pearson correlation
+    and the root mean square distance of the two sets of unperturbed settled states over the counted rows and the regulated
+    genes --, scores_spearman -- the Spearman correlation of the per-knockout means of the magnitude over the genes other
+    than the held one --, n_unconverged -- the rows left out --, true, learned)."""
+    genes = [int(g) for g in genes]
+    K = len(genes)
+    tb, lb = _host_array(true.base.y).astype(np.float64), _host_array(learned.base.y).astype(np.float64)
+    tk, lk = _host_array(true.knockouts.y).astype(np.float64), _host_array(learned.knockouts.y).astype(np.float64)
+    if tb.ndim != 2 or tb.shape != lb.shape or tk.shape != lk.shape or tk.shape != (K * tb.shape[0], tb.shape[1]):
+        raise ValueError("steady_state_recovery_scores: the two screens must hold the same [B, N] states and [%d B, N] "
+                         "knockout rows, got %s, %s and %s, %s" % (K, tb.shape, tk.shape, lb.shape, lk.shape))
+    B, N = tb.shape
+    regulated = np.ones(N, bool) if regulated is None else np.asarray(regulated, bool).reshape(-1)
+    if regulated.shape != (N,):
+        raise ValueError("steady_state_recovery_scores: regulated must be bool [%d]" % N)
+    ok_b = (_host_array(true.base.status) == 0) & (_host_array(learned.base.status) == 0)
+    ok_k = ((_host_array(true.knockouts.status) == 0) & (_host_array(learned.knockouts.status) == 0)).reshape(K, B)
+    shifts = []
+    for kb, base in ((tk, tb), (lk, lb)):
+        d = kb.reshape(K, B, N) - base[None, :, :]
+        w = (ok_k & ok_b[None, :]).astype(np.float64)[:, :, None]
+        with np.errstate(invalid="ignore"):
+            shifts.append(((d * w).sum(axis=1) / w.sum(axis=1), (np.abs(d) * w).sum(axis=1) / w.sum(axis=1)))
+    s = knockout_recovery_scores(genes, shifts[0][0], shifts[1][0], min_effect)
+    a, b = tb[ok_b][:, regulated].reshape(-1), lb[ok_b][:, regulated].reshape(-1)
+    rms = float(np.sqrt(np.mean((a - b) ** 2))) if len(a) else float("nan")
+    others = np.ones((K, N), bool)
+    others[np.arange(K), genes] = False
+    with np.errstate(invalid="ignore"):
+        mean_mag = [np.where(others, m, 0.0).sum(axis=1) / others.sum(axis=1) for m in (shifts[0][1], shifts[1][1])]
+    live = np.isfinite(mean_mag[0]) & np.isfinite(mean_mag[1])
+    rank = _pearson(_average_ranks(mean_mag[0][live]), _average_ranks(mean_mag[1][live]))
+    return SteadyStateRecovery(genes, s.n_entries, s.sign_agreement, s.pearson, s.spearman, s.slope, s.per_gene,
+                               _pearson(a, b), rms, rank, int((~ok_b).sum() + (~ok_k).sum()), true, learned)
+
+
+def steady_state_recovery(odenet, system, y0, genes, value=0.0, min_effect=0.0, **steady_kw):
+    """Does a model trained on in-silico data settle where the simulator settles, with and without a gene held?  The model's
+    `steady.knockout_steady_states(odenet, y0, genes, value)` is held against the truth, `system.knockout_steady_states` (a
+    `HillSystem`: the same states, genes and levels), by `steady_state_recovery_scores` with the system's regulated genes;
+    steady_kw: tol, max_iter, tau0 of both.  Where `knockout_recovery` asks about the first unit of time after an
+    intervention, this asks about its final outcome.  Returns the SteadyStateRecovery of the two screens.
+    ValueError before any launch when the model's gene count is not `system.N`."""
+    from . import steady
+    N = params_of(odenet)[0].shape[1]
+    if N != system.N:
+        raise ValueError("steady_state_recovery: the model has %d genes, the system %d" % (N, system.N))
+    if set(steady_kw) - {"tol", "max_iter", "tau0"}:
+        raise TypeError("steady_state_recovery: unexpected arguments %s" % sorted(set(steady_kw) - {"tol", "max_iter", "tau0"}))
+    genes = engine.int_list("steady_state_recovery", genes)
+    engine.check_genes("steady_state_recovery", genes, N)
+    learned = steady.knockout_steady_states(odenet, y0, genes, value, **steady_kw)
+    true = system.knockout_steady_states(y0, genes, value, **steady_kw)
+    return steady_state_recovery_scores(genes, true, learned, ~system.is_input, min_effect)
+
+
 # ------------------------------------------------------------------ pathway permutation tests (SURVEY.md row 22)
 def consolidate_gene_scores(gene_names, scores):
     """One score per gene symbol from one score per array entry (create_permutation_test_files_aws.R:68-84).  An entry

@@ -19,6 +19,10 @@ at a level, `HillSystem.knockout_effects` scores such a screen as `analysis.knoc
 ground truth of `analysis.knockout_recovery`; `rates_reference` / `knockouts_reference` restate them in numpy (section 8j).
 A call may hold a SET of up to four genes (`phx_hill_knockout_sets`): `HillSystem.knockout_pairs` is the truth of
 `analysis.knockout_pairs` and its epistasis score, `analysis.epistasis_recovery` scores a model against it (section 8l).
+And where it settles: `HillSystem.steady_states` / `knockout_steady_states` (`phx_hill_steady`, `csrc/phx_hillss.hip`) relax
+states to the system's attractors by the iteration of `steady.steady_states`, a step being a forward substitution over the
+strongly connected components of the network (`block_structure`); `steady_states_reference` restates it in numpy, and
+`analysis.steady_state_recovery` scores a model's settled states against it (section 8p).
 """
 import ast
 import collections
@@ -289,6 +293,8 @@ def read_ode_system(path):
 
 HillPattern = collections.namedtuple("HillPattern", ("regulator", "target", "ptr"))
 HillJacobian = collections.namedtuple("HillJacobian", ("regulator", "target", "value"))
+HillBlocks = collections.namedtuple("HillBlocks", ("order", "comp_ptr", "level_ptr", "largest"))
+SCC_MAX = 64     # PHX_HILL_SCC_MAX: the largest strongly connected component phx_hill_steady solves
 JACOBIAN_MODES = {None: 0, "mean": 1, "mean_abs": 2}     # `mode` of phx_hill_jacobian
 OP_HILL_JACOBIAN = 11    # workspace-cache key of HillSystem.jacobian (phx_hill_jacobian_workspace_bytes sizes it)
 
@@ -392,7 +398,7 @@ class HillSystem:
         self.code_host = np.asarray(code, np.int32).reshape(-1, 2)
         self.consts_host = np.asarray(consts, np.float64)
         self.off_host, self.len_host = np.asarray(off, np.int32), np.asarray(length, np.int32)
-        self._pattern = self._pattern_dev = None
+        self._pattern = self._pattern_dev = self._blocks = self._blocks_dev = self._targets_of = None
         self.device = torch.device(device)
         if self.device.type == "cuda":
             self.code = torch.from_numpy(self.code_host).to(self.device)
@@ -638,6 +644,268 @@ class HillSystem:
                                                  engine._p(value), engine._p(ws), nbytes, engine._stream_ptr()))
         return HillJacobian(regulator, target, value)
 
+    # ---- the attractors
+    def block_structure(self):
+        """The schedule of the steady-state solve, on the host from `jacobian_pattern()` with self-edges ignored:
+        HillBlocks(order int32 [N], comp_ptr int32 [C + 1], level_ptr int32 [L + 1], largest).  The strongly connected
+        components of the regulatory graph (an iterative Tarjan) are levelled at 1 + the highest level of a component that
+        regulates them (0 without one; "input gene" rows are one-gene components at level 0); order lists the genes by
+        component (ascending within one), the components by level (by their smallest gene within one);
+        order[comp_ptr[c]:comp_ptr[c + 1]] is component c, components level_ptr[l]:level_ptr[l + 1] are level l; largest is
+        the size of the largest component.  Every regulator of a gene lies in its own component or at a lower level, so
+        apart from its diagonal the Jacobian is block lower triangular in `order`.  One schedule per system: a held or
+        frozen gene only removes edges."""
+        if self._blocks is None:
+            pat, N = self.jacobian_pattern(), self.N
+            regs = [[r for r in pat.regulator[pat.ptr[j]:pat.ptr[j + 1]].tolist() if r != j] for j in range(N)]
+            # Tarjan on the graph target -> regulator: a component is finished after every component that regulates it
+            index, low, comp = [-1] * N, [0] * N, [-1] * N
+            on_stack, stack, comps, count = [False] * N, [], [], 0
+            for root in range(N):
+                if index[root] >= 0:
+                    continue
+                index[root] = low[root] = count
+                count += 1
+                stack.append(root)
+                on_stack[root] = True
+                work = [(root, 0)]
+                while work:
+                    v, i = work.pop()
+                    if i < len(regs[v]):
+                        work.append((v, i + 1))
+                        w = regs[v][i]
+                        if index[w] < 0:
+                            index[w] = low[w] = count
+                            count += 1
+                            stack.append(w)
+                            on_stack[w] = True
+                            work.append((w, 0))
+                        elif on_stack[w]:
+                            low[v] = min(low[v], index[w])
+                        continue
+                    if low[v] == index[v]:
+                        members = []
+                        while True:
+                            w = stack.pop()
+                            on_stack[w] = False
+                            comp[w] = len(comps)
+                            members.append(w)
+                            if w == v:
+                                break
+                        comps.append(sorted(members))
+                    if work:
+                        low[work[-1][0]] = min(low[work[-1][0]], low[v])
+            level = []
+            for c, members in enumerate(comps):        # in this order the regulators of a component come before it
+                level.append(1 + max((level[comp[r]] for g in members for r in regs[g] if comp[r] != c), default=-1))
+            by_level = sorted(range(len(comps)), key=lambda c: (level[c], comps[c][0]))
+            order = np.asarray([g for c in by_level for g in comps[c]], np.int32)
+            comp_ptr = np.zeros(len(comps) + 1, np.int32)
+            np.cumsum([len(comps[c]) for c in by_level], out=comp_ptr[1:])
+            n_level = max(level) + 1 if level else 0
+            level_ptr = np.searchsorted(np.asarray([level[c] for c in by_level]), np.arange(n_level + 1)).astype(np.int32)
+            self._blocks = HillBlocks(order, comp_ptr, level_ptr, max((len(m) for m in comps), default=0))
+        return self._blocks
+
+    def _blocks_on_device(self):
+        """(order, comp_ptr, level_ptr) int32 of `block_structure()` on the system's device"""
+        if self._blocks_dev is None:
+            blk = self.block_structure()
+            self._blocks_dev = tuple(torch.from_numpy(a).to(self.code.device) for a in blk[:3])
+        return self._blocks_dev
+
+    def _blocks_fit(self):
+        """does phx_hill_steady take this system: no component above PHX_HILL_SCC_MAX, vectors within its LDS budget"""
+        blk = self.block_structure()
+        E = len(self.jacobian_pattern().regulator)
+        return 1 <= blk.largest <= SCC_MAX and _lib.load().phx_hill_steady_lds_bytes(self.N, E, blk.largest) > 0
+
+    def reached(self, gene):
+        """bool [N] on the host: the genes whose rate depends on `gene` directly or through others (a graph search on
+        `jacobian_pattern()` without its diagonal); `gene` itself only where a cycle leads back to it"""
+        if self._targets_of is None:
+            pat = self.jacobian_pattern()
+            self._targets_of = [[] for _ in range(self.N)]
+            for r, t in zip(pat.regulator.tolist(), pat.target.tolist()):
+                if r != t:
+                    self._targets_of[r].append(t)
+        seen, todo = np.zeros(self.N, bool), [int(gene)]
+        while todo:
+            for t in self._targets_of[todo.pop()]:
+                if not seen[t]:
+                    seen[t] = True
+                    todo.append(t)
+        return seen
+
+    def _steady_blocks(self, x, free, tol, max_iter, tau0):
+        """phx_hill_steady on checked arguments: x [R, N] float32 contiguous, free [R, N] bool, both on the device"""
+        R, N, dev = x.shape[0], self.N, x.device
+        eptr, ereg = self._pattern_on_device()[:2]
+        order, comp_ptr, level_ptr = self._blocks_on_device()
+        moving = free.to(torch.uint8).contiguous()
+        y = torch.empty_like(x)
+        rho, tau = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(2))
+        its, status = (torch.empty(R, dtype=torch.int32, device=dev) for _ in range(2))
+        p = engine._p
+        engine._check_call(_lib.load().phx_hill_steady(
+            *self._args(), p(eptr), p(ereg), ereg.shape[0], p(order), p(comp_ptr), comp_ptr.shape[0] - 1, p(level_ptr),
+            level_ptr.shape[0] - 1, self.block_structure().largest, p(x), p(moving), R, N, float(tol), int(max_iter), float(tau0),
+            p(y), p(rho), p(its), p(status), p(tau), engine._stream_ptr()))
+        return y, rho, its, status, tau
+
+    def _steady_dense(self, x, free, tol, max_iter, tau0):
+        """the same iteration from `rhs`, `jacobian` and a dense float64 solve of the N x N systems of all rows at once;
+        control per row on the device as in `steady._iterate`, nothing is read back"""
+        from . import steady
+        B, N, dev = x.shape[0], self.N, x.device
+        regulator, target = self._pattern_on_device()[2:]
+        zero = x.new_zeros(())
+
+        def rates(y):
+            return torch.where(free, self.rhs(y), zero)
+
+        f = rates(x)
+        rho = f.abs().amax(dim=1)                                  # (amax hands a NaN on)
+        tau = torch.full((B,), float(tau0), dtype=torch.float32, device=dev)
+        status = torch.where(rho <= tol, steady.CONVERGED, steady.MAX_ITER).to(torch.int32)
+        its = torch.zeros(B, dtype=torch.int32, device=dev)
+        diag = torch.arange(N, device=dev)
+        for _ in range(int(max_iter)):
+            active = status == steady.MAX_ITER
+            A = torch.zeros((B, N, N), dtype=torch.float64, device=dev)
+            A[:, target, regulator] = -self.jacobian(x).value.double()
+            A = A * free.unsqueeze(2)                              # a gene that does not move: the row of delta = 0
+            A[:, diag, diag] += torch.where(free, (1 / tau).unsqueeze(1), x.new_ones(())).double()
+            d, info = torch.linalg.solve_ex(A, f.double().unsqueeze(2))
+            d = d.squeeze(2).float()
+            bad = active & ((info != 0) | ~torch.isfinite(d).all(dim=1))
+            xc = torch.where(free & (active & ~bad).unsqueeze(1), x + d, x)
+            fc = rates(xc)
+            rhoc = fc.abs().amax(dim=1)
+            ok = active & ~bad & torch.isfinite(rhoc) & (rhoc <= 2 * rho)
+            rejected = active & ~bad & ~ok
+            tau = torch.where(ok, tau * torch.clamp(rho / rhoc, 2.0, 10.0), torch.where(rejected, tau / 4, tau))
+            x = torch.where(ok.unsqueeze(1), xc, x)
+            f = torch.where(ok.unsqueeze(1), fc, f)
+            rho = torch.where(ok, rhoc, rho)
+            its = its + active.to(torch.int32)
+            status = torch.where(bad, steady.SINGULAR, torch.where(ok & (rhoc <= tol), steady.CONVERGED, status)).to(torch.int32)
+        return x.clone() if int(max_iter) == 0 else x, rho, its, status, tau
+
+    def _steady_control(self, name, tol, max_iter, tau0, method):
+        """the checks of the control arguments, on the host -> the route, "blocks" or "dense" """
+        from . import steady
+        steady._check_control(name, tol, max_iter, tau0)
+        if method not in (None, "blocks", "dense"):
+            raise ValueError('%s: method must be None, "blocks" or "dense", got %r' % (name, method))
+        if method == "dense":
+            return method
+        fits = self._blocks_fit()
+        if method == "blocks" and not fits:
+            raise ValueError("%s: method=\"blocks\" takes components of up to %d genes and a system whose vectors fit its "
+                             "LDS; this one's largest component has %d of %d genes: use method=\"dense\""
+                             % (name, SCC_MAX, self.block_structure().largest, self.N))
+        return "blocks" if fits else "dense"
+
+    def _steady_run(self, x, free, tol, max_iter, tau0, route, rows_per_call=None):
+        from . import steady
+        if len(self.jacobian_pattern().regulator) == 0:            # input genes only: nothing moves, nothing to launch
+            B, dev = x.shape[0], x.device
+            return steady.SteadyStates(x.clone(), torch.zeros(B, device=dev), torch.zeros(B, dtype=torch.int32, device=dev),
+                                       torch.zeros(B, dtype=torch.int32, device=dev),
+                                       torch.full((B,), float(tau0), device=dev), None)
+        if route == "blocks":
+            step, run = steady.MAX_ROWS if rows_per_call is None else rows_per_call, self._steady_blocks
+        else:
+            step, run = max(1, min(steady.MAX_ROWS, steady.SOLVE_BYTES // (24 * self.N * self.N))), self._steady_dense
+            step = step if rows_per_call is None else min(step, rows_per_call)
+        parts = [run(x[r0:r0 + step], free[r0:r0 + step], float(tol), max_iter, tau0) for r0 in range(0, x.shape[0], step)]
+        return steady.SteadyStates(*((torch.cat(c) for c in zip(*parts)) if len(parts) > 1 else parts[0]), None)
+
+    def _moving(self, name, sets, frozen, B, device):
+        """bool [B, N] on the device: gene n moves in row b -- it has a program, is not in the row's held set, not frozen"""
+        free = np.repeat(~self.is_input[None, :], B, axis=0)
+        for b, s in enumerate(sets):
+            free[b, list(s)] = False
+        if frozen is not None:
+            free &= ~np.broadcast_to(frozen, free.shape)
+        return torch.from_numpy(free).to(device)
+
+    def _frozen(self, name, frozen, B):
+        if frozen is None:
+            return None
+        fz = frozen.detach().cpu().numpy() if isinstance(frozen, torch.Tensor) else np.asarray(frozen)
+        if fz.dtype != np.bool_ or fz.shape not in ((self.N,), (B, self.N)):
+            raise ValueError("%s: frozen must be bool [%d] or [%d, %d], got %s %s" % (name, self.N, B, self.N, fz.dtype, fz.shape))
+        return fz
+
+    def steady_states(self, x0, clamp=None, frozen=None, tol=1e-5, max_iter=50, tau0=1.0, method=None):
+        """The attractors of the system itself: the steady states the rows of x0 ([B, N] or [B, 1, N] float32 on the device)
+        relax to -- the truth `steady.steady_states` of a model trained on this system's data is scored against.  A gene
+        moves in row b if it has a rate expression, is not in row b's held set (`clamp`: per row up to four genes held at
+        their x0 values, in the forms the model's function takes, -1 / () for none) and is not `frozen` (bool [B, N] or [N]);
+        every other gene keeps its x0 bits.  The iteration and its control are those of the model's function, to the letter
+        (rho = max |rate| over the moving genes; done at rho <= tol; a step of (I / tau - J) delta = f is accepted iff the new
+        rho' is finite and <= 2 rho, then tau <- tau min(10, max(2, rho / rho')), else tau <- tau / 4; tau0 = inf: Newton).
+        method="blocks": phx_hill_steady, one launch, a workgroup per row; a step is a forward substitution over the
+        strongly connected components of the network (`block_structure()`), which must have at most 64 genes each; a row's
+        bits depend on nothing but that row.  method="dense": the same iteration from `rhs`, `jacobian` and
+        torch.linalg.solve_ex on [B, N, N] float64, rows in blocks within `steady.SOLVE_BYTES`; its bits may depend on the
+        batch.  None: "blocks" where the system fits, else "dense".
+        Returns `steady.SteadyStates(y, residual, iterations, status, tau, reduced=None)` of device tensors; status 0
+        converged, 1 max_iter reached, 2 a zero or non-finite pivot or divisor.  Argument errors are raised on the host
+        before any device call."""
+        from . import steady
+        name = "steady_states"
+        route = self._steady_control(name, tol, max_iter, tau0, method)
+        x2 = steady._rows(name, x0, self.N)
+        B = x2.shape[0]
+        sets = steady._held_sets(name, clamp, B, self.N)
+        frozen = self._frozen(name, frozen, B)
+        x2 = self._knockout_x0(name, x2)
+        with torch.no_grad():
+            return self._steady_run(x2, self._moving(name, sets, frozen, B, x2.device), tol, max_iter, tau0, route)
+
+    def knockout_steady_states(self, x0, genes, value=0.0, rows_per_call=4096, **steady_kw):
+        """Where does the SYSTEM settle when gene g is held at `value`: `steady.knockout_steady_states` on the simulator, the
+        truth of that screen.  The unperturbed states of x0 are solved once; knockout k restarts from them with column
+        genes[k] set to value[k] (a scalar or one level per gene) and held, and only the genes that genes[k] reaches
+        (`reached`) move: a gene it does not reach cannot change and keeps the baseline's bits, so shift and magnitude are
+        exactly 0 there.  The K B rows are solved in blocks of `rows_per_call`; steady_kw: tol, max_iter, tau0, method.
+        Returns `steady.KnockoutSteadyStates(genes, base, knockouts, shift [K, N], magnitude [K, N])` as the model's."""
+        from . import steady
+        name, N = "knockout_steady_states", self.N
+        if set(steady_kw) - {"tol", "max_iter", "tau0", "method"}:
+            raise TypeError("%s: unexpected arguments %s" % (name, sorted(set(steady_kw) - {"tol", "max_iter", "tau0", "method"})))
+        genes = engine.int_list(name, genes)
+        engine.check_genes(name, genes, N)
+        if not genes:
+            raise ValueError("%s: no gene to hold" % name)
+        values = engine.gene_values(name, value, len(genes))
+        for v in values:
+            if not np.isfinite(np.float32(v)):
+                raise ValueError("%s: level %r is not a finite float32" % (name, v))
+        if isinstance(rows_per_call, bool) or not hasattr(rows_per_call, "__index__") or int(rows_per_call) < 1:
+            raise ValueError("%s: rows_per_call must be a positive integer" % name)
+        kw = dict(dict(tol=1e-5, max_iter=50, tau0=1.0, method=None), **steady_kw)
+        route = self._steady_control(name, kw["tol"], kw["max_iter"], kw["tau0"], kw["method"])
+        x2 = self._knockout_x0(name, steady._rows(name, x0, N))
+        B, K, dev = x2.shape[0], len(genes), x2.device
+        with torch.no_grad():
+            base = self._steady_run(x2, self._moving(name, [()] * B, None, B, dev), kw["tol"], kw["max_iter"], kw["tau0"], route)
+            start = base.y.unsqueeze(0).repeat(K, 1, 1)
+            free = np.zeros((K, N), bool)
+            for k, (gene, v) in enumerate(zip(genes, values)):
+                start[k, :, gene] = v
+                free[k] = self.reached(gene) & ~self.is_input
+                free[k, gene] = False
+            free = torch.from_numpy(free).to(dev).unsqueeze(1).expand(K, B, N).reshape(K * B, N)
+            ko = self._steady_run(start.reshape(K * B, N), free, kw["tol"], kw["max_iter"], kw["tau0"], route,
+                                  min(int(rows_per_call), steady.MAX_ROWS))
+            d = ko.y.reshape(K, B, N) - base.y.unsqueeze(0)
+            shift, magnitude = d.mean(dim=1), d.abs().mean(dim=1)
+        return steady.KnockoutSteadyStates(genes, base, ko, shift, magnitude)
+
     def sample_initial(self, numsamples, output_gene_var=1.0, rng=None, input_models=None, cor_strength=5.0,
                        input_gene_var=1.0, prop_bimodal=0.0):
         """Initial states of `simDataset` (SimulationGRN_core_init_var.R:165-213).  Regulated genes: Beta(2/var, 2/var)
@@ -818,6 +1086,149 @@ def knockouts_reference(system, x0, times, genes, values, dt_max, dtype=np.float
             y = y + (h / six) * acc
         out.append(y.copy())
     return np.stack(out)
+
+
+def _lu_solve(A, b):
+    """A x = b in float64 by LU with partial pivoting as phx_hill_steady does it (the first largest |a| of a column, a NaN
+    wins; elimination by rows, back substitution by columns) -> (x, bad): bad for a pivot that is 0 or not finite"""
+    A, b = np.array(A, np.float64), np.array(b, np.float64)
+    n = len(b)
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            col = A[k:, k]
+            key = np.where(np.isnan(col), np.inf, np.abs(col))
+            p = k + int(np.argmax(key))
+            if not key[p - k] > 0 or np.isinf(key[p - k]):
+                return np.zeros(n), True
+            if p != k:
+                A[[k, p]] = A[[p, k]]
+                b[[k, p]] = b[[p, k]]
+            fac = A[k + 1:, k] / A[k, k]
+            A[k + 1:, k + 1:] -= fac[:, None] * A[k, k + 1:][None, :]
+            b[k + 1:] -= fac * b[k]
+        for k in range(n - 1, -1, -1):
+            b[k] = b[k] / A[k, k]
+            b[:k] -= A[:k, k] * b[k]
+    return b, False
+
+
+def block_substitution(system, J, f, sigma, moving=None, dtype=np.float64):
+    """(sigma I - J) delta = f of ONE state by the forward substitution of phx_hill_steady over `system.block_structure()`,
+    in numpy: J [E] on `system.jacobian_pattern()`, f [N]; a one-gene component is delta_j = (f_j + sum_{k != j} J_jk
+    delta_k) / (sigma - J_jj) in `dtype`, the row's entries ascending; a larger one assembles its block in float64 and solves
+    it by LU with partial pivoting (`_lu_solve`).  A gene with moving[n] false has delta 0 whatever J and f say.
+    Returns (delta [N] in `dtype`, bad): bad for a pivot or a divisor that is 0 or not finite."""
+    dt = np.dtype(dtype).type
+    blk, pat, N = system.block_structure(), system.jacobian_pattern(), system.N
+    moving = np.ones(N, bool) if moving is None else np.asarray(moving, bool)
+    J, f, sigma = np.asarray(J, dt), np.asarray(f, dt), dt(sigma)
+    order, ptr, reg = blk.order.tolist(), pat.ptr.tolist(), pat.regulator.tolist()
+    pos = np.empty(N, np.int64)
+    pos[blk.order] = np.arange(N)
+    d, bad = np.zeros(N, dt), False
+    with np.errstate(all="ignore"):
+        for c in range(len(blk.comp_ptr) - 1):              # by level: every regulator outside the component is done
+            o, n = int(blk.comp_ptr[c]), int(blk.comp_ptr[c + 1] - blk.comp_ptr[c])
+            if n == 1:
+                g = order[o]
+                if not moving[g]:
+                    continue
+                acc, jd = f[g], dt(0)
+                for e in range(ptr[g], ptr[g + 1]):
+                    if reg[e] == g:
+                        jd = J[e]
+                    else:
+                        acc = acc + J[e] * d[reg[e]]
+                div = sigma - jd
+                bad = bad or not abs(div) > 0 or bool(np.isinf(div))
+                d[g] = acc / div
+                continue
+            A, b = np.zeros((n, n)), np.zeros(n)
+            for i, g in enumerate(order[o:o + n]):
+                if not moving[g]:
+                    A[i, i] = 1.0
+                    continue
+                A[i, i] = float(sigma)
+                acc = float(f[g])
+                for e in range(ptr[g], ptr[g + 1]):
+                    rk = int(pos[reg[e]]) - o
+                    if 0 <= rk < n:
+                        A[i, rk] -= float(J[e])
+                    else:
+                        acc += float(J[e]) * float(d[reg[e]])
+                b[i] = acc
+            x, singular = _lu_solve(A, b)
+            bad = bad or singular
+            d[order[o:o + n]] = x.astype(dt)
+    return d, bad
+
+
+def steady_states_reference(system, x0, clamp=None, frozen=None, tol=1e-5, max_iter=50, tau0=1.0, dtype=np.float64,
+                            solve="dense"):
+    """`HillSystem.steady_states` in numpy on the host, for a system on any device: the same iteration and control on
+    `rates_reference` / `jacobian_reference` in `dtype`.  solve="blocks" restates the kernel's level-by-level substitution
+    (`block_substitution`); solve="dense" solves the N x N system (rows of genes that do not move replaced by delta = 0) with
+    np.linalg.solve in float64.  x0 [B, N] or [B, 1, N]; clamp, frozen as there.  Returns `steady.SteadyStates` of numpy
+    arrays, reduced None."""
+    from . import steady
+    name = "steady_states_reference"
+    steady._check_control(name, tol, max_iter, tau0)
+    if solve not in ("dense", "blocks"):
+        raise ValueError('%s: solve must be "dense" or "blocks", got %r' % (name, solve))
+    dt = np.dtype(dtype).type
+    N = system.N
+    x = np.array(x0, dtype=dt)
+    if not ((x.ndim == 2 and x.shape[1] == N) or (x.ndim == 3 and x.shape[1:] == (1, N))) or x.shape[0] < 1:
+        raise ValueError("%s: x0 must be [B, %d] or [B, 1, %d], got %s" % (name, N, N, x.shape))
+    x = x.reshape(x.shape[0], N)
+    B = x.shape[0]
+    free = system._moving(name, steady._held_sets(name, clamp, B, N), system._frozen(name, frozen, B), B, "cpu").numpy()
+    pat = system.jacobian_pattern()
+    row_moves = free[:, pat.target]                           # [B, E]: the entry's target moves
+
+    def state(y):
+        with np.errstate(all="ignore"):
+            f = np.where(free, rates_reference(system, y, dt), dt(0))
+            return f, np.abs(f).max(axis=1)
+
+    f, rho = state(x)
+    tau = np.full(B, tau0, dt)
+    status = np.where(rho <= tol, steady.CONVERGED, steady.MAX_ITER).astype(np.int32)
+    its = np.zeros(B, np.int32)
+    for _ in range(int(max_iter)):
+        active = status == steady.MAX_ITER
+        if not active.any():
+            break
+        xc, bad = x.copy(), np.zeros(B, bool)
+        with np.errstate(all="ignore"):
+            J = np.where(row_moves, jacobian_reference(system, x, dt), dt(0))
+            sigma = (1 / tau).astype(dt)
+            for b in np.nonzero(active)[0]:
+                if solve == "blocks":
+                    d, bad[b] = block_substitution(system, J[b], f[b], sigma[b], free[b], dt)
+                else:
+                    A = np.zeros((N, N))
+                    A[pat.target, pat.regulator] = -J[b].astype(np.float64)
+                    A[np.arange(N), np.arange(N)] += np.where(free[b], float(sigma[b]), 1.0)
+                    try:
+                        if not np.all(np.isfinite(A)):
+                            raise np.linalg.LinAlgError
+                        d = np.linalg.solve(A, f[b].astype(np.float64)).astype(dt)
+                        if not np.all(np.isfinite(d)):
+                            raise np.linalg.LinAlgError
+                    except np.linalg.LinAlgError:
+                        bad[b] = True
+                if not bad[b]:
+                    xc[b] = np.where(free[b], x[b] + d, x[b])
+            fc, rhoc = state(xc)
+            ok = active & ~bad & np.isfinite(rhoc) & (rhoc <= 2 * rho)
+            rejected = active & ~bad & ~ok
+            grow = np.clip(rho / np.where(rhoc > 0, rhoc, dt(1e-300) if dt is np.float64 else dt(1e-45)), 2, 10).astype(dt)
+            tau = np.where(ok, tau * grow, np.where(rejected, tau / 4, tau)).astype(dt)
+        x[ok], f[ok], rho[ok] = xc[ok], fc[ok], rhoc[ok]
+        its += active
+        status = np.where(bad, steady.SINGULAR, np.where(ok & (rhoc <= tol), steady.CONVERGED, status)).astype(np.int32)
+    return steady.SteadyStates(x, rho, its, status, tau, None)
 
 
 def generate_dataset(system, numsamples, time_stamps=(0.0, 2.0, 3.0, 7.0, 9.0), expnoise=0.0, dt_max=0.01, rng=None,
