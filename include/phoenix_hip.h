@@ -700,6 +700,43 @@ size_t phx_steady_solve_workspace_bytes(int H, int B);
 int phx_steady_solve(const float *S, const float *w, int H, int B, float *x, int *info, void *workspace, size_t workspace_bytes,
                      void *stream);
 
+/* The implicit adjoint of that solve (phoenix_amd.steady_states(differentiable=True)).  A steady state
+ * satisfies P r(y*) = 0, (I - P) y* = (I - P) y0 with r(y) = Wa h(y) - y and P = diag(m), m = 1 on the genes that move and 0 on
+ * the others.  With gy = dL/dy* [B, N], per row:
+ *     b = WaT (m gy),   (I - S^T) q = b   (S of phx_reduced_jacobian at y* with this m; phx_steady_solve on its transpose),
+ *     u = gy + C^T q,   lam = m u,   dL/dy0 = (1 - m) u
+ * and the parameter gradients are sums over the rows: dWa[n, c] = sum lam[b, n] hid[b, c], dWs[j, n] = sum q[b, j] a[b, n],
+ * dWp[j, n] = sum q[b, H + j] v[b, j] l[b, n], dbs[j] = sum q[b, j], dbp[j] = sum q[b, H + j] v[b, j], dg = 0 (a fixed point
+ * does not depend on the size of a positive multiplier).  phx_steady_adj.hip; all arrays float on the device.
+ * phx_steady_adjoint_project: b [B, 2H].  A contraction over the genes, v_mfma_f32_16x16x4_f32, 64 rows x 64 columns per
+ *   workgroup; the gene axis is cut into min(ceil(N / 32), 8) segments, a function of N alone, whose partial blocks
+ *   (workspace: phx_steady_adjoint_project_workspace_bytes(N, H, B)) a second kernel adds in ascending order.  A gene with
+ *   m == 0 is not read into any sum, whatever gy holds there.  A row's bits depend neither on B nor on the other rows.
+ * phx_steady_adjoint_back: lam [B, N] and gy0 [B, N] from y, m, gy, q [B, 2H] and hid [B, 2H] (phx_reduced_jacobian's).  One
+ *   thread per gene, j ascending, a' and l' recomputed from y.  lam is exactly 0 where m == 0, gy0 exactly 0 where m != 0.
+ *   B <= 65535.
+ * phx_steady_param_grads: the five products from y, lam, q, hid into `grads`, which is honoured as phx_rhs_vjp honours it
+ *   (overwrite, Wa or WaT); grads->g is written 0 under overwrite and left untouched otherwise.  The products are one
+ *   [4H] x (N + 1) block (gene N is a column of ones: the bias sums) and the contraction runs over the rows:
+ *   v_mfma_f32_16x16x4_f32, a workgroup owns 64 columns x 64 genes and walks its rows 32 at a time, a and l recomputed once
+ *   per (row, gene) of a chunk.  The rows are cut into max(1, min(ceil(B / 32) / 2, ceil(512 / blocks))) segments, a function
+ *   of (N, H, B) alone; finishing kernels add the segments' partial blocks (workspace:
+ *   phx_steady_param_grads_workspace_bytes(N, H, B)) in ascending order and write every output element once.  A row with
+ *   lam = 0 and q = 0 contributes exact zeros.
+ * No atomics anywhere: two runs give the same bits.  Nothing allocates or synchronises.  1 <= H <= 256, N >= 1, B >= 1.
+ * PHX_ERR_BAD_ARG before any device call for a null pointer (p, the parameter arrays a call reads, any array argument,
+ * grads, grads->Ws / bs / Wp / bp, both of grads->Wa and grads->WaT, grads->g under overwrite) or a shape outside those
+ * ranges.  PHX_ERR_WORKSPACE when workspace is null or workspace_bytes is below the call's *_workspace_bytes (0 for a shape
+ * the call refuses). */
+size_t phx_steady_adjoint_project_workspace_bytes(int N, int H, int B);
+int phx_steady_adjoint_project(const phx_params *p, const float *m, const float *gy, int B, float *b, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int phx_steady_adjoint_back(const phx_params *p, const float *y, const float *m, const float *gy, const float *q, const float *hid,
+                            int B, float *lam, float *gy0, void *stream);
+size_t phx_steady_param_grads_workspace_bytes(int N, int H, int B);
+int phx_steady_param_grads(const phx_params *p, const float *y, const float *lam, const float *q, const float *hid, int B,
+                           const phx_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

@@ -47,7 +47,9 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_odeint_clamped_rows_workspace_bytes", "phx_odeint_clamped_rows",
            "phx_odeint_adjoint_backward_clamped_rows", "phx_debug_clamped_rows_plan",
            "phx_reduced_jacobian_workspace_bytes", "phx_reduced_jacobian", "phx_steady_residual", "phx_steady_update",
-           "phx_steady_solve_workspace_bytes", "phx_steady_solve", "phx_hill_steady_lds_bytes", "phx_hill_steady")
+           "phx_steady_solve_workspace_bytes", "phx_steady_solve", "phx_hill_steady_lds_bytes", "phx_hill_steady",
+           "phx_steady_adjoint_project_workspace_bytes", "phx_steady_adjoint_project", "phx_steady_adjoint_back",
+           "phx_steady_param_grads_workspace_bytes", "phx_steady_param_grads")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -212,6 +214,16 @@ def load():
         lib.phx_hill_steady_lds_bytes.restype = C.c_size_t
         lib.phx_hill_steady.argtypes = [vp] * 6 + [C.c_longlong, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int,
                                         C.c_double, C.c_int, C.c_double, vp, vp, vp, vp, vp, vp]
+    # (the same: an earlier build of ABI 7 has no steady-state adjoint)
+    if path == _build.LIB or hasattr(lib, "phx_steady_param_grads"):
+        lib.phx_steady_adjoint_project_workspace_bytes.argtypes = [C.c_int] * 3
+        lib.phx_steady_adjoint_project_workspace_bytes.restype = C.c_size_t
+        lib.phx_steady_adjoint_project.argtypes = [C.POINTER(PhxParams), vp, vp, C.c_int, vp, vp, C.c_size_t, vp]
+        lib.phx_steady_adjoint_back.argtypes = [C.POINTER(PhxParams), vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+        lib.phx_steady_param_grads_workspace_bytes.argtypes = [C.c_int] * 3
+        lib.phx_steady_param_grads_workspace_bytes.restype = C.c_size_t
+        lib.phx_steady_param_grads.argtypes = [C.POINTER(PhxParams), vp, vp, vp, vp, C.c_int, C.POINTER(PhxGrads), vp, C.c_size_t,
+                                               vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

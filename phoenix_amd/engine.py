@@ -1473,3 +1473,67 @@ def steady_solve(S, w):
     ws = _analysis_workspace(OP_STEADY_SOLVE, nbytes, w.device)
     _check_call(_lib.load().phx_steady_solve(_p(S), _p(w), n // 2, B, _p(x), _p(info), _p(ws), nbytes, _stream_ptr()))
     return x, info
+
+
+OP_STEADY_PROJECT = 17     # workspace-cache key of steady_adjoint_project (phx_steady_adjoint_project_workspace_bytes)
+OP_STEADY_PGRADS = 18      # ... and of steady_param_grads (phx_steady_param_grads_workspace_bytes)
+
+
+def _steady_hidden(name, p, x, B, what):
+    """`x` as contiguous float32 [B, 2H] on the device"""
+    _require_gpu(x, what)
+    if tuple(x.shape) != (B, 2 * p.H):
+        raise ValueError("%s: %s must be [%d, %d], got %s" % (name, what, B, 2 * p.H, tuple(x.shape)))
+    return x.detach().contiguous()
+
+
+def steady_adjoint_project(p, m, gy):
+    """b [B, 2H] = WaT (m gy) of the cotangents gy [B, N] and the weights m [B, N] (exact 0: the gene is not read):
+    phx_steady_adjoint_project"""
+    m2 = _steady_rows("steady_adjoint_project", p, m, "m")
+    g2 = _steady_rows("steady_adjoint_project", p, gy, "gy")
+    if m2.shape != g2.shape:
+        raise ValueError("steady_adjoint_project: m and gy must have one shape")
+    B, dev = m2.shape[0], m2.device
+    b = torch.empty((B, 2 * p.H), dtype=torch.float32, device=dev)
+    p.on_current_stream()
+    nbytes = _ws_size((OP_STEADY_PROJECT, p.N, p.H, B), "phx_steady_adjoint_project_workspace_bytes", p.N, p.H, B)
+    ws = _analysis_workspace(OP_STEADY_PROJECT, nbytes, dev)
+    _check_call(_lib.load().phx_steady_adjoint_project(C.byref(p.c), _p(m2), _p(g2), B, _p(b), _p(ws), nbytes, _stream_ptr()))
+    return b
+
+
+def steady_adjoint_back(p, y, m, gy, q, hid):
+    """(lam [B, N] = m (gy + C(y)^T q), gy0 [B, N] = (1 - m) (gy + C(y)^T q)) with q, hid [B, 2H]: phx_steady_adjoint_back"""
+    name = "steady_adjoint_back"
+    y2, m2, g2 = _steady_rows(name, p, y), _steady_rows(name, p, m, "m"), _steady_rows(name, p, gy, "gy")
+    if m2.shape != y2.shape or g2.shape != y2.shape:
+        raise ValueError("%s: y, m and gy must have one shape" % name)
+    B = y2.shape[0]
+    q2, h2 = _steady_hidden(name, p, q, B, "q"), _steady_hidden(name, p, hid, B, "hid")
+    lam, gy0 = torch.empty_like(y2), torch.empty_like(y2)
+    p.on_current_stream()
+    _check_call(_lib.load().phx_steady_adjoint_back(C.byref(p.c), _p(y2), _p(m2), _p(g2), _p(q2), _p(h2), B, _p(lam), _p(gy0),
+                                                    _stream_ptr()))
+    return lam, gy0
+
+
+def steady_param_grads(p, y, lam, q, hid, grads=None):
+    """phx_steady_param_grads: the parameter gradients of the rows y, lam [B, N], q, hid [B, 2H] as `Grads`.  `grads`: a
+    `Grads` of an earlier call (of another block of rows) to add to; None: a fresh one, written."""
+    name = "steady_param_grads"
+    y2, l2 = _steady_rows(name, p, y), _steady_rows(name, p, lam, "lam")
+    if l2.shape != y2.shape:
+        raise ValueError("%s: y and lam must have one shape" % name)
+    B, dev = y2.shape[0], y2.device
+    q2, h2 = _steady_hidden(name, p, q, B, "q"), _steady_hidden(name, p, hid, B, "hid")
+    if grads is None:
+        grads = p.new_grads()
+    else:
+        grads.c.overwrite = 0
+    p.on_current_stream()
+    nbytes = _ws_size((OP_STEADY_PGRADS, p.N, p.H, B), "phx_steady_param_grads_workspace_bytes", p.N, p.H, B)
+    ws = _analysis_workspace(OP_STEADY_PGRADS, nbytes, dev)
+    _check_call(_lib.load().phx_steady_param_grads(C.byref(p.c), _p(y2), _p(l2), _p(q2), _p(h2), B, C.byref(grads.c), _p(ws), nbytes,
+                                                   _stream_ptr()))
+    return grads

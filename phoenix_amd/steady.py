@@ -5,7 +5,14 @@ plus a product through the 2H-wide hidden vector, so a linearly implicit (Rosenb
     m = tau g+ / (1 + tau g+),   delta = m (r + Wa x),   (I - S) x = w,   S = C(y) diag(m) Wa,   w = C(y) (m r),   r = Wa h(y) - y
 costs one contraction over the genes (phx_reduced_jacobian, the MFMA kernel of phx_steady.hip), two RHS-sized passes and a
 2H x 2H dense solve.  With tau small the step follows the ODE and stays in the basin of y0; as tau grows it becomes Newton's.
-`steady_states_reference` is the same iteration in numpy, without a GPU."""
+`steady_states_reference` is the same iteration in numpy, without a GPU.
+
+`steady_states(differentiable=True)` carries a gradient (section 8q): the steady state satisfies P r(y*) = 0, (I - P) y* =
+(I - P) y0 with P = diag(1 on the moving genes), so by the implicit function theorem, with gy = dL/dy*,
+    b = Wa^T (m gy),   (I - S^T) q = b,   u = gy + C^T q,   lam = m u,   dL/dy0 = (1 - m) u
+and the parameter gradients are the outer products of (lam, hid), (q, a) and (q v, l) summed over the rows: one transposed
+2H x 2H solve per row and RHS-sized passes, no time integration (phx_steady_adj.hip).  `steady_states_adjoint_reference` is
+the same in numpy."""
 import collections
 import math
 
@@ -18,10 +25,12 @@ from .odenet import params_of
 
 SteadyStates = collections.namedtuple("SteadyStates", ("y", "residual", "iterations", "status", "tau", "reduced"))
 KnockoutSteadyStates = collections.namedtuple("KnockoutSteadyStates", ("genes", "base", "knockouts", "shift", "magnitude"))
+SteadyAdjoint = collections.namedtuple("SteadyAdjoint", ("y0", "Ws", "bs", "Wp", "bp", "Wa", "g", "lam", "q", "info"))
 
 CONVERGED, MAX_ITER, SINGULAR = 0, 1, 2      # SteadyStates.status
 MAX_ROWS = 32768                             # rows of one pass of the iteration: more are solved in blocks
 SOLVE_BYTES = 256 << 20                      # ... and so are rows whose dense systems would take more workspace than this
+NOT_CONVERGED = -2                           # last_backward_info(): the row's forward status was not CONVERGED
 
 
 def _check_control(name, tol, max_iter, tau0):
@@ -118,7 +127,82 @@ def _iterate(p, y, free, gpos, tol, max_iter, tau0):
     return y, rho, its, status, tau
 
 
-def steady_states(odenet, y0, clamp=None, tol=1e-5, max_iter=50, tau0=1.0, return_reduced=False):
+def _block_rows(p):
+    return max(1, min(MAX_ROWS, SOLVE_BYTES // (32 * p.H * p.H)))      # the dense solve holds (2H)^2 doubles per row
+
+
+def _relax(p, y, free, gpos, tol, max_iter, tau0):
+    """`_iterate` on all rows, in blocks of `_block_rows` -> (y, rho, its, status, tau)"""
+    step = _block_rows(p)
+    parts = [_iterate(p, y[b0:b0 + step], free[b0:b0 + step], gpos, float(tol), max_iter, tau0)
+             for b0 in range(0, y.shape[0], step)]
+    y, rho, its, status, tau = (torch.cat(c) for c in zip(*parts)) if len(parts) > 1 else parts[0]
+    if max_iter == 0:
+        y = y.clone()
+    return y, rho, its, status, tau
+
+
+_last_info = None
+
+
+def last_backward_info():
+    """info [B] int32 on the device of the most recent backward pass through `steady_states(differentiable=True)` (None
+    before the first): 0 the row's gradient was used, -2 (`NOT_CONVERGED`) its forward status was not CONVERGED, otherwise
+    phx_steady_solve's info of the transposed system (k + 1: no pivot in column k, -1: a non-finite solution) -- the row
+    sits at a bifurcation.  The backward pass does not synchronise; reading this tensor does."""
+    return _last_info
+
+
+class _SteadyFn(torch.autograd.Function):
+    """y* of `steady_states` with the implicit adjoint as its backward (once differentiable)"""
+
+    @staticmethod
+    def forward(ctx, y0, ctl, ws, bs, wp, bp, wa, g):
+        p, y, free, gpos, tol, max_iter, tau0 = ctl
+        out = _relax(p, y, free, gpos, tol, max_iter, tau0)
+        ctx.set_materialize_grads(False)
+        ctx.phx_params = p
+        ctx.phx_versions = tuple(x._version for x in (ws, bs, wp, bp, wa, g))
+        ctx.phx_y0_shape = y0.shape
+        ctx.save_for_backward(out[0], free, out[3], ws, bs, wp, bp, wa, g)
+        ctx.mark_non_differentiable(*out[1:])
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, *_unused):
+        global _last_info
+        if gy is None:
+            return (None,) * 8
+        y, free, status, ws, bs, wp, bp, wa, g = ctx.saved_tensors
+        p = ctx.phx_params
+        if ctx.phx_versions != tuple(x._version for x in (ws, bs, wp, bp, wa, g)):
+            p = engine.params_cached(ws, bs, wp, bp, wa, g)   # parameters were modified in place since forward
+        need_p = any(ctx.needs_input_grad[2:8])
+        gy = gy.reshape(y.shape).contiguous()
+        zero = y.new_zeros(())
+        step, grads, gy0s, infos = _block_rows(p), None, [], []
+        for b0 in range(0, y.shape[0], step):
+            yb, gb, fb = y[b0:b0 + step], gy[b0:b0 + step], free[b0:b0 + step]
+            conv = status[b0:b0 + step] == CONVERGED
+            S, _w, hid = engine.reduced_jacobian(p, yb, fb.to(torch.float32))
+            b = engine.steady_adjoint_project(p, fb.to(torch.float32), gb)
+            q, info = engine.steady_solve(S.transpose(1, 2).contiguous(), b)
+            # a row that is no fixed point, or whose transposed system is singular, has no gradient: m and q are zeroed
+            valid = (conv & (info == 0)).unsqueeze(1)
+            m = (fb & valid).to(torch.float32)
+            q = torch.where(valid, q, zero)
+            lam, gy0 = engine.steady_adjoint_back(p, yb, m, gb, q, hid)
+            gy0s.append(torch.where(valid, gy0, zero))
+            infos.append(torch.where(conv, info, NOT_CONVERGED).to(torch.int32))
+            if need_p:       # (the state and the hidden vector of such a row may be non-finite: 0 x them must stay 0)
+                grads = engine.steady_param_grads(p, torch.where(valid, yb, zero), lam, q, torch.where(valid, hid, zero), grads)
+        _last_info = torch.cat(infos) if len(infos) > 1 else infos[0]
+        gy0 = (torch.cat(gy0s) if len(gy0s) > 1 else gy0s[0]).reshape(ctx.phx_y0_shape) if ctx.needs_input_grad[0] else None
+        return (gy0, None) + (tuple(grads.as_reference_layout(g.shape)) if need_p else (None,) * 6)
+
+
+def steady_states(odenet, y0, clamp=None, tol=1e-5, max_iter=50, tau0=1.0, return_reduced=False, differentiable=False):
     """The steady states the rows of y0 ([B, N] or [B, 1, N] float32 on the device) relax to.  A gene moves in row b if
     relu(g) > 0 and it is not in row b's held set; `clamp` has the meaning and the forms it has in `odeint` (up to four genes
     per row, -1 / () for none).  Every other gene keeps its y0 value to the bit; the module is never modified.
@@ -128,16 +212,28 @@ def steady_states(odenet, y0, clamp=None, tol=1e-5, max_iter=50, tau0=1.0, retur
     tau0 = float("inf") is plain Newton.  All max_iter passes are issued without a host synchronisation.
     Returns SteadyStates(y [B, N], residual [B] (rho of y), iterations [B] int32 (steps tried), status [B] int32 -- 0
     converged, 1 max_iter reached, 2 a singular or non-finite I - S --, tau [B], reduced): device tensors; reduced is S
-    [B, 2H, 2H] with m = 1 on the moving genes at the result where return_reduced, else None."""
+    [B, 2H, 2H] with m = 1 on the moving genes at the result where return_reduced, else None.
+    differentiable=True: the same iteration and the same values, but `y` carries a gradient to y0 and to the six parameter
+    tensors of the module (the other fields stay plain tensors): the implicit adjoint of the fixed point (section 8q), one
+    transposed 2H x 2H solve per row, no time integration.  The gradient of g is exactly 0 (a fixed point does not depend on
+    the size of a positive multiplier), the gradient of y0 is exactly 0 on the genes that move (the attractor does not depend
+    on where in its basin the row started) and dL/d(the level the gene is held at) on the others.  Only a converged row is a
+    fixed point: MASK THE LOSS with `status == 0`.  A row that is not converged, or whose transposed system is singular (a
+    bifurcation), contributes exact zeros to every gradient whatever the loss says; `last_backward_info()` tells which.
+    The backward pass does not synchronise.  Once differentiable: no double backward; not for `GraphedStep` capture;
+    `knockout_steady_states` stays without a gradient."""
     _check_control("steady_states", tol, max_iter, tau0)
+    if differentiable:
+        tensors = params_of(odenet)
+        with torch.no_grad():
+            p, y, free, gpos = _setup("steady_states", odenet, y0, clamp)
+        y, rho, its, status, tau = _SteadyFn.apply(y0, (p, y, free, gpos, tol, max_iter, tau0), *tensors)
+        with torch.no_grad():
+            reduced = engine.reduced_jacobian(p, y.detach(), free.to(torch.float32))[0] if return_reduced else None
+        return SteadyStates(y, rho, its, status, tau, reduced)
     with torch.no_grad():
         p, y, free, gpos = _setup("steady_states", odenet, y0, clamp)
-        step = max(1, min(MAX_ROWS, SOLVE_BYTES // (32 * p.H * p.H)))      # the dense solve holds (2H)^2 doubles per row
-        parts = [_iterate(p, y[b0:b0 + step], free[b0:b0 + step], gpos, float(tol), max_iter, tau0)
-                 for b0 in range(0, y.shape[0], step)]
-        y, rho, its, status, tau = (torch.cat(c) for c in zip(*parts)) if len(parts) > 1 else parts[0]
-        if max_iter == 0:
-            y = y.clone()
+        y, rho, its, status, tau = _relax(p, y, free, gpos, tol, max_iter, tau0)
         reduced = engine.reduced_jacobian(p, y, free.to(torch.float32))[0] if return_reduced else None
     return SteadyStates(y, rho, its, status, tau, reduced)
 
@@ -272,3 +368,55 @@ def steady_states_reference(params, y0, clamp=None, tol=1e-5, max_iter=50, tau0=
         status = np.where(bad, SINGULAR, np.where(ok & (rhoc <= tol), CONVERGED, status)).astype(np.int32)
     reduced = np.stack([(C_of(b, d) * free[b][None, :].astype(dt)) @ wa for b in range(B)])
     return SteadyStates(y, rho, its, status, tau, reduced)
+
+
+def steady_states_adjoint_reference(params, y, gy, clamp=None, status=None, dtype=np.float64):
+    """The gradients `steady_states(differentiable=True)` returns, in numpy and without a GPU: the formulas of section 8q
+    at the steady states y [B, N] for the cotangents gy [B, N] = dL/dy, the arithmetic in `dtype` (the transposed 2H x 2H
+    solve in float64 either way).  params, clamp as in `steady_states_reference`; status [B] (optional): a row whose
+    status is not 0 contributes exact zeros.  Returns SteadyAdjoint(y0 [B, N], Ws [H, N], bs, Wp, bp, Wa [N, 2H], g [N]
+    (zeros), lam [B, N], q [B, 2H], info [B] int32 -- 0 used, -2 status != 0, 1 a singular transposed system, -1 a
+    non-finite solution)."""
+    dt = np.dtype(dtype).type
+    ws, bs, wp, bp, wa, g = _np_params(params, dt)
+    H, N = ws.shape
+    y = np.array(y, dtype=dt).reshape(-1, N)
+    gy = np.array(gy, dtype=dt).reshape(-1, N)
+    B = y.shape[0]
+    if gy.shape != y.shape:
+        raise ValueError("steady_states_adjoint_reference: y and gy must have one shape")
+    sets = _held_sets("steady_states_adjoint_reference", clamp, B, N)
+    free = np.repeat((g > 0)[None, :], B, axis=0)
+    for b, s in enumerate(sets):
+        free[b, list(s)] = False
+    info = np.zeros(B, np.int32)
+    if status is not None:
+        info[np.asarray(status).reshape(B) != 0] = NOT_CONVERGED
+    with np.errstate(all="ignore"):
+        a, l, da, dl, u, v = _np_parts(ws, bs, wp, bp, y)
+    q, lam, gy0 = np.zeros((B, 2 * H), dt), np.zeros((B, N), dt), np.zeros((B, N), dt)
+    eye = np.eye(2 * H)
+    for b in np.nonzero(info == 0)[0]:
+        C = np.concatenate([ws * da[b][None, :], v[b][:, None] * wp * dl[b][None, :]], axis=0)
+        S = (C * free[b][None, :].astype(dt)) @ wa
+        rhs = wa.T @ np.where(free[b], gy[b], dt(0))
+        A = eye - S.T.astype(np.float64)
+        try:
+            if not np.all(np.isfinite(A)):
+                raise np.linalg.LinAlgError
+            x = np.linalg.solve(A, rhs.astype(np.float64))
+        except np.linalg.LinAlgError:
+            info[b] = 1
+            continue
+        if not np.all(np.isfinite(x)):
+            info[b] = -1
+            continue
+        q[b] = x.astype(dt)
+        w = gy[b] + q[b] @ C
+        lam[b] = np.where(free[b], w, dt(0))
+        gy0[b] = np.where(free[b], dt(0), w)
+    used = (info == 0)[:, None]
+    hid = np.where(used, np.concatenate([u, v], axis=1), dt(0))
+    qv = q[:, H:] * hid[:, H:]
+    return SteadyAdjoint(gy0, q[:, :H].T @ np.where(used, a, dt(0)), q[:, :H].sum(axis=0), qv.T @ np.where(used, l, dt(0)),
+                         qv.sum(axis=0), lam.T @ hid, np.zeros(N, dt), lam, q, info)
