@@ -737,6 +737,41 @@ size_t phx_steady_param_grads_workspace_bytes(int N, int H, int B);
 int phx_steady_param_grads(const phx_params *p, const float *y, const float *lam, const float *q, const float *hid, int B,
                            const phx_grads *grads, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The network of total effects at a fixed point (phoenix_amd.steady_state_response).  On the moving
+ * genes r(y) + u = 0, so (I - M Wa C) dy = M du with M = diag(m), m = 1 on the genes that move in the row and 0 elsewhere,
+ * and by the Woodbury identity of section 8o
+ *     R = dy / du = M + M Wa Z C M,   Z = (I - S)^-1 (2H x 2H),   S = C M Wa   (phx_reduced_jacobian with this m).
+ * Holding gene k and moving its level gives dy / d(level k) = R[:, k] / R[k, k].  phx_steady_resp.hip; all arrays on the
+ * device, float unless said otherwise.
+ * phx_steady_inverse: Z [B, 2H, 2H] float = (I - S_b)^-1, computed in double by LU with partial pivoting on [I - S | I],
+ *   one workgroup per state, the pivot rule and the info codes of phx_steady_solve (0; k + 1: column k has no finite
+ *   non-zero pivot; -1: the inverse is not finite; Z_b = 0 for both).  Workspace: phx_steady_inverse_workspace_bytes(H, B)
+ *   = 2 B (2H)^2 doubles.
+ * phx_steady_response_factors: for the K regulators genes[k] (int, 0 <= gene < N, device) and every state the column
+ *   x_bk = Z_b C_b[:, gene] = a'(y) (Z_b[:, :H] Ws[:, gene]) + l'(y) ((Z_b[:, H:] diag hid_b[H:]) Wp[:, gene]), y = y[b, gene]:
+ *   v_mfma_f32_16x16x4_f32 over the hidden index ascending, the two halves in accumulators of their own so that a' and l'
+ *   are applied once per (b, k).  A second pass forms d_bk = 1 + m_bk sum_c WaT[c, gene] x_bk[c] (c ascending) and scales
+ *   the column by m_bk (input 0, "production") or 1 / d_bk (input 1, "level").  X [B, 2H, K], use [B, K] (1.0: the row is
+ *   used for this regulator; 0.0 where info[b] != 0 or d_bk is 0 or not finite: the column is then exactly 0).  A column
+ *   of the weights that is exactly 0 gives an exactly-zero column.  K >= 1, B <= 65535.
+ * phx_steady_response: out [K, N] (row stride ld >= N), out[k, j] = the mean over the used states of
+ *   m_bj sum_c WaT[c, j] X_b[c, k] (absolute values where mean_abs != 0), plus m_bk on the diagonal j = genes[k] for input
+ *   0; for input 1 the diagonal is exactly 1 (0 where no state is used).  The mean divides by sum_b use[b, k], read on the
+ *   device (by 1 where that is 0).  One workgroup owns 64 regulators x 64 targets in accumulators over all the states and
+ *   stores the tile once: no N x N temporary, no atomics; sums over c ascending, then b ascending; a regulator's row does
+ *   not depend on the other regulators of the call.  X is walked 32 rows at a time through a double buffer in LDS, the
+ *   chunk after the current one requested before the current one's products; the WaT panel stays in LDS where the whole
+ *   workgroup stays within 64 KiB (H <= 64) and is streamed with the X chunks otherwise.  A target with m_bj = 0 gets an
+ *   exact 0 from state b.
+ * 1 <= H <= 256, N >= 1, B >= 1.  PHX_ERR_BAD_ARG before any device call for a null pointer, a shape outside the ranges, an
+ * input outside {0, 1} or ld < N; PHX_ERR_WORKSPACE as above.  Nothing allocates or synchronises. */
+size_t phx_steady_inverse_workspace_bytes(int H, int B);
+int phx_steady_inverse(const float *S, int H, int B, float *Z, int *info, void *workspace, size_t workspace_bytes, void *stream);
+int phx_steady_response_factors(const phx_params *p, const float *y, const float *m, const float *hid, const float *Z,
+                                const int *info, int B, const int *genes, int K, int input, float *X, float *use, void *stream);
+int phx_steady_response(const phx_params *p, const float *m, const float *X, const float *use, int B, const int *genes, int K,
+                        int input, int mean_abs, float *out, long long ld, void *stream);
+
 /* Diagnostic only (not part of the drop-in surface): with PHX_PROF=1 in the environment the v1 kernels
  * write 16 per-workgroup segment timers (100 MHz ticks) into the workspace; this returns where. */
 /* Diagnostic only: the next phx_odeint / phx_odeint_adjoint_backward call on this thread records these two

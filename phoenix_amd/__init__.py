@@ -21,8 +21,9 @@ from .analysis import (Edges, EpistasisPerPair, EpistasisRecovery, EpistasisReco
                        write_permutation_table, SteadyStateRecovery, steady_state_recovery, steady_state_recovery_scores)
 from .simulator import (HillBlocks, HillJacobian, HillPattern, HillSystem, block_substitution,  # noqa: F401
                         generate_dataset, jacobian_reference, knockouts_reference, rates_reference)
-from .steady import (KnockoutSteadyStates, SteadyAdjoint, SteadyStates, knockout_steady_states,  # noqa: F401
+from .steady import (KnockoutSteadyStates, SteadyAdjoint, SteadyResponse, SteadyStates,  # noqa: F401
+                     knockout_steady_states,
                      last_backward_info, reduced_jacobian, steady_states, steady_states_adjoint_reference,
-                     steady_states_reference)
+                     steady_state_response, steady_state_response_reference, steady_states_reference)
 
 __version__ = "0.1.0"

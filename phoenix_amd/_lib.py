@@ -49,7 +49,8 @@ EXPORTS = ("phx_abi_version", "phx_status_string", "phx_device_cus", "phx_worksp
            "phx_reduced_jacobian_workspace_bytes", "phx_reduced_jacobian", "phx_steady_residual", "phx_steady_update",
            "phx_steady_solve_workspace_bytes", "phx_steady_solve", "phx_hill_steady_lds_bytes", "phx_hill_steady",
            "phx_steady_adjoint_project_workspace_bytes", "phx_steady_adjoint_project", "phx_steady_adjoint_back",
-           "phx_steady_param_grads_workspace_bytes", "phx_steady_param_grads")
+           "phx_steady_param_grads_workspace_bytes", "phx_steady_param_grads",
+           "phx_steady_inverse_workspace_bytes", "phx_steady_inverse", "phx_steady_response_factors", "phx_steady_response")
 
 OP_RHS_FORWARD, OP_RHS_VJP, OP_ODEINT, OP_ADJOINT = 0, 1, 2, 3
 METHODS = {"euler": 0, "midpoint": 1, "rk4": 2, "dopri5": 3}
@@ -224,6 +225,15 @@ def load():
         lib.phx_steady_param_grads_workspace_bytes.restype = C.c_size_t
         lib.phx_steady_param_grads.argtypes = [C.POINTER(PhxParams), vp, vp, vp, vp, C.c_int, C.POINTER(PhxGrads), vp, C.c_size_t,
                                                vp]
+    # (the same: an earlier build of ABI 7 has no steady-state response)
+    if path == _build.LIB or hasattr(lib, "phx_steady_response"):
+        lib.phx_steady_inverse_workspace_bytes.argtypes = [C.c_int] * 2
+        lib.phx_steady_inverse_workspace_bytes.restype = C.c_size_t
+        lib.phx_steady_inverse.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_size_t, vp]
+        lib.phx_steady_response_factors.argtypes = [C.POINTER(PhxParams), vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp,
+                                                    vp]
+        lib.phx_steady_response.argtypes = [C.POINTER(PhxParams), vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp,
+                                            C.c_longlong, vp]
     assert lib.phx_abi_version() == 7
     _LIB = lib
     return lib

@@ -1537,3 +1537,72 @@ def steady_param_grads(p, y, lam, q, hid, grads=None):
     _check_call(_lib.load().phx_steady_param_grads(C.byref(p.c), _p(y2), _p(l2), _p(q2), _p(h2), B, C.byref(grads.c), _p(ws), nbytes,
                                                    _stream_ptr()))
     return grads
+
+
+OP_STEADY_INVERSE = 19     # workspace-cache key of steady_inverse (phx_steady_inverse_workspace_bytes)
+RESPONSE_INPUTS = {"production": 0, "level": 1}       # phx_steady_response_factors / phx_steady_response: input
+
+
+def steady_inverse(S):
+    """(Z [B, n, n] float32 = (I - S_b)^-1 computed in float64 on the device, info [B] int32 -- phx_steady_solve's codes; Z_b = 0
+    where info[b] != 0): phx_steady_inverse"""
+    _require_gpu(S, "S")
+    if S.dim() != 3 or S.shape[1] != S.shape[2] or S.shape[1] % 2 or S.shape[0] < 1:
+        raise ValueError("steady_inverse: S must be [B, 2H, 2H], got %s" % (tuple(S.shape),))
+    S = S.detach().contiguous()
+    B, n = S.shape[0], S.shape[1]
+    Z = torch.empty_like(S)
+    info = torch.empty(B, dtype=torch.int32, device=S.device)
+    nbytes = _ws_size((OP_STEADY_INVERSE, n, B), "phx_steady_inverse_workspace_bytes", n // 2, B)
+    ws = _analysis_workspace(OP_STEADY_INVERSE, nbytes, S.device)
+    _check_call(_lib.load().phx_steady_inverse(_p(S), n // 2, B, _p(Z), _p(info), _p(ws), nbytes, _stream_ptr()))
+    return Z, info
+
+
+def _response_genes(name, p, genes):
+    _require_gpu(genes, "genes")
+    if genes.dtype != torch.int32 or genes.dim() != 1 or genes.numel() < 1:
+        raise ValueError("%s: genes must be a non-empty int32 vector on the device" % name)
+    return genes.contiguous()
+
+
+def steady_response_factors(p, y, m, hid, Z, info, genes, input):
+    """(X [B, 2H, K], use [B, K]) of phx_steady_response_factors: the columns Z_b C_b[:, genes[k]], scaled by m_bk
+    (input "production") or 1 / d_bk ("level"); a column of a row with info != 0 or a d that is 0 or not finite is 0, use 0.
+    genes: int32 [K] on the device, every entry one of 0 .. N - 1 (the caller has checked them on the host)."""
+    name = "steady_response_factors"
+    y2, m2 = _steady_rows(name, p, y), _steady_rows(name, p, m, "m")
+    B, H2, dev = y2.shape[0], 2 * p.H, y2.device
+    if m2.shape != y2.shape or tuple(Z.shape) != (B, H2, H2) or tuple(info.shape) != (B,) or info.dtype != torch.int32:
+        raise ValueError("%s: y, m [B, N], Z [B, 2H, 2H] and info [B] int32 do not go together" % name)
+    h2 = _steady_hidden(name, p, hid, B, "hid")
+    _require_gpu(Z, "Z")
+    g = _response_genes(name, p, genes)
+    K = g.numel()
+    X = torch.empty((B, H2, K), dtype=torch.float32, device=dev)
+    use = torch.empty((B, K), dtype=torch.float32, device=dev)
+    p.on_current_stream()
+    _check_call(_lib.load().phx_steady_response_factors(C.byref(p.c), _p(y2), _p(m2), _p(h2), _p(Z.detach().contiguous()),
+                                                        _p(info.contiguous()), B, _p(g), K, RESPONSE_INPUTS[input], _p(X), _p(use),
+                                                        _stream_ptr()))
+    return X, use
+
+
+def steady_response(p, m, X, use, genes, input, mean_abs, out=None):
+    """phx_steady_response: out [K, N], the mean over the used states of m_bj sum_c WaT[c, j] X_b[c, k] (of its absolute value
+    where mean_abs), with the diagonal of the input (see the header).  out: a [K, N] float32 view with contiguous rows (a
+    block of rows of a larger matrix) to write into; None: a new tensor."""
+    name = "steady_response"
+    m2 = _steady_rows(name, p, m, "m")
+    g = _response_genes(name, p, genes)
+    B, K = m2.shape[0], g.numel()
+    if tuple(X.shape) != (B, 2 * p.H, K) or tuple(use.shape) != (B, K) or not X.is_contiguous() or not use.is_contiguous():
+        raise ValueError("%s: X must be contiguous [%d, %d, %d] and use [%d, %d]" % (name, B, 2 * p.H, K, B, K))
+    if out is None:
+        out = torch.empty((K, p.N), dtype=torch.float32, device=m2.device)
+    if tuple(out.shape) != (K, p.N) or out.dtype != torch.float32 or out.stride(1) != 1 or out.stride(0) < p.N or not out.is_cuda:
+        raise ValueError("%s: out must be float32 [%d, %d] with contiguous rows on the device" % (name, K, p.N))
+    p.on_current_stream()
+    _check_call(_lib.load().phx_steady_response(C.byref(p.c), _p(m2), _p(X), _p(use), B, _p(g), K, RESPONSE_INPUTS[input],
+                                                1 if mean_abs else 0, _p(out), out.stride(0), _stream_ptr()))
+    return out

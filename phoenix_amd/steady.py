@@ -12,7 +12,12 @@ costs one contraction over the genes (phx_reduced_jacobian, the MFMA kernel of p
     b = Wa^T (m gy),   (I - S^T) q = b,   u = gy + C^T q,   lam = m u,   dL/dy0 = (1 - m) u
 and the parameter gradients are the outer products of (lam, hid), (q, a) and (q v, l) summed over the rows: one transposed
 2H x 2H solve per row and RHS-sized passes, no time integration (phx_steady_adj.hip).  `steady_states_adjoint_reference` is
-the same in numpy."""
+the same in numpy.
+
+`steady_state_response` is the network of total effects at the fixed points (section 8r): on the moving genes r(y) + u = 0,
+so R = dy*/du = M + M Wa Z C M with Z = (I - S)^-1 and M = diag(1 on the moving genes) -- every regulator's answer from one
+2H x 2H inverse per state, reduced over the states by a kernel that never forms an N x N temporary (phx_steady_resp.hip).
+`steady_state_response_reference` is the same in numpy."""
 import collections
 import math
 
@@ -26,6 +31,7 @@ from .odenet import params_of
 SteadyStates = collections.namedtuple("SteadyStates", ("y", "residual", "iterations", "status", "tau", "reduced"))
 KnockoutSteadyStates = collections.namedtuple("KnockoutSteadyStates", ("genes", "base", "knockouts", "shift", "magnitude"))
 SteadyAdjoint = collections.namedtuple("SteadyAdjoint", ("y0", "Ws", "bs", "Wp", "bp", "Wa", "g", "lam", "q", "info"))
+SteadyResponse = collections.namedtuple("SteadyResponse", ("regulators", "response", "scores", "info"))
 
 CONVERGED, MAX_ITER, SINGULAR = 0, 1, 2      # SteadyStates.status
 MAX_ROWS = 32768                             # rows of one pass of the iteration: more are solved in blocks
@@ -277,6 +283,88 @@ def knockout_steady_states(odenet, y0, genes, value=0.0, rows_per_call=256, **st
     return KnockoutSteadyStates(genes, base, ko, shift, magnitude)
 
 
+def _response_args(name, N, regulators, input, reduce, rows_bytes=1):
+    """the host checks `steady_state_response` and its reference share -> the regulators as a list"""
+    if input not in ("level", "production"):
+        raise ValueError('%s: input must be "level" or "production", got %r' % (name, input))
+    if reduce not in ("mean_abs", "mean"):
+        raise ValueError('%s: reduce must be "mean_abs" or "mean", got %r' % (name, reduce))
+    if isinstance(rows_bytes, bool) or not hasattr(rows_bytes, "__index__") or int(rows_bytes) < 1:
+        raise ValueError("%s: rows_bytes must be a positive integer" % name)
+    regs = list(range(N)) if regulators is None else engine.int_list(name, regulators, "regulators")
+    engine.check_genes(name, regs, N)
+    if not regs:
+        raise ValueError("%s: no regulator" % name)
+    return regs
+
+
+def _response_status(name, status, B):
+    if status is None:
+        return None
+    if not torch.is_tensor(status):
+        status = torch.as_tensor(np.asarray(status))
+    if tuple(status.shape) != (B,) or status.is_floating_point() or status.is_complex():
+        raise ValueError("%s: status must be [%d] integers, got %s %s" % (name, B, status.dtype, tuple(status.shape)))
+    return status
+
+
+def _response_scores(response, regs, N, xp):
+    """mean of |response[i, j]| over the targets j != regulators[i]"""
+    mag = xp.abs(response)
+    at = xp.arange(len(regs))
+    own = mag[at, regs if xp is np else torch.as_tensor(regs, device=response.device)]
+    return (mag.sum(1) - own) / max(N - 1, 1)
+
+
+def steady_state_response(odenet, y, clamp=None, regulators=None, input="level", reduce="mean_abs", status=None,
+                          rows_bytes=256 << 20):
+    """If gene i moves, where do all the other genes settle?  The network of total effects at the states y ([B, N] or
+    [B, 1, N] float32 on the device, normally `steady_states(...).y`), every indirect path followed to the end (section 8r):
+    on the moving genes r(y) + u = 0, so R = dy*/du = M + M Wa Z C M with Z = (I - S)^-1 -- all N answers of a state from one
+    2H x 2H factorisation.  `clamp` as in `steady_states`; `regulators`: the K genes whose input moves (default all N).
+    input="production": response[i, j] reduces R_b[j, regulators[i]], the shift of target j per unit of extra production of
+    the regulator (exactly 0 for a regulator that does not move in row b).  input="level": the regulator is held and its
+    LEVEL moves, R_b[j, i] / R_b[i, i]: exactly 1 at j = i, and for a regulator the row already holds the quantity
+    `y0.grad[b, i]` of `steady_states(differentiable=True)` carries.  reduce: the mean over the used states of the entries
+    ("mean") or of their absolute values ("mean_abs").  A row is left out -- it contributes exact zeros and the mean divides
+    by the rest, counted on the device -- where I - S_b is singular or not finite, where `status` ([B] integers, e.g.
+    `SteadyStates.status`) is not 0, and, for one regulator only, where its divisor d_bi = 1 + m_bi Wa[i, :] x_bi is 0 or
+    not finite.  A target that moves in no used row is exactly 0 off the diagonal.
+    Returns SteadyResponse(regulators, response [K, N] (regulator -> target), scores [K] (the mean of |response[i, j]| over
+    j != regulators[i]; for `consolidate_gene_scores`), info [B] int32: 0 the row was used, -2 (`NOT_CONVERGED`) its status
+    was not 0, else phx_steady_solve's code of I - S_b).  Device tensors; nothing is read back.  The regulators are walked in
+    blocks whose factors [B, 2H, K_block] stay under `rows_bytes`; a block's rows have the bits of the full result."""
+    name = "steady_state_response"
+    tensors = params_of(odenet)
+    N = tensors[0].shape[1]
+    regs = _response_args(name, N, regulators, input, reduce, rows_bytes)
+    y2 = _rows(name, y, N)
+    B, K = y2.shape[0], len(regs)
+    status = _response_status(name, status, B)
+    with torch.no_grad():
+        p, y2, free, _ = _setup(name, odenet, y2, clamp)
+        dev = y2.device
+        m = free.to(torch.float32)
+        step = max(1, _block_rows(p) // 2)           # the inverse holds 2 (2H)^2 doubles per row
+        parts = []
+        for b0 in range(0, B, step):
+            S, _w, hid = engine.reduced_jacobian(p, y2[b0:b0 + step], m[b0:b0 + step])
+            parts.append((hid,) + engine.steady_inverse(S))
+        hid, Z, info = (torch.cat(c) for c in zip(*parts)) if len(parts) > 1 else parts[0]
+        if status is not None:
+            info = torch.where(status.to(dev) != 0, NOT_CONVERGED, info).to(torch.int32)
+        genes = torch.tensor(regs, dtype=torch.int32, device=dev)
+        block = max(1, int(rows_bytes) // (B * 2 * p.H * 4))
+        if block >= 64:
+            block = block // 64 * 64                 # whole tiles of the hot kernel
+        response = torch.empty((K, N), dtype=torch.float32, device=dev)
+        for k0 in range(0, K, block):
+            X, use = engine.steady_response_factors(p, y2, m, hid, Z, info, genes[k0:k0 + block], input)
+            engine.steady_response(p, m, X, use, genes[k0:k0 + block], input, reduce == "mean_abs", response[k0:k0 + block])
+        scores = _response_scores(response, regs, N, torch)
+    return SteadyResponse(regs, response, scores, info)
+
+
 # --------------------------------------------------------------------------------------------- the reference, no GPU
 def _np_params(params, dtype):
     if isinstance(params, dict):
@@ -420,3 +508,60 @@ def steady_states_adjoint_reference(params, y, gy, clamp=None, status=None, dtyp
     qv = q[:, H:] * hid[:, H:]
     return SteadyAdjoint(gy0, q[:, :H].T @ np.where(used, a, dt(0)), q[:, :H].sum(axis=0), qv.T @ np.where(used, l, dt(0)),
                          qv.sum(axis=0), lam.T @ hid, np.zeros(N, dt), lam, q, info)
+
+
+def steady_state_response_reference(params, y, clamp=None, regulators=None, input="level", reduce="mean_abs", status=None,
+                                    dtype=np.float64):
+    """`steady_state_response` in numpy without a GPU: the same formulas at the states y [B, N], the arithmetic in `dtype`
+    (the 2H x 2H inverse in float64 either way).  params, clamp as in `steady_states_reference`.  Returns SteadyResponse of
+    numpy arrays; info is 0, -2 (status != 0), 1 (a singular I - S_b, whatever its column) or -1 (a non-finite inverse)."""
+    name = "steady_state_response_reference"
+    dt = np.dtype(dtype).type
+    ws, bs, wp, bp, wa, g = _np_params(params, dt)
+    H, N = ws.shape
+    regs = _response_args(name, N, regulators, input, reduce)
+    y = np.array(y, dtype=dt).reshape(-1, N)
+    B, K = y.shape[0], len(regs)
+    sets = _held_sets(name, clamp, B, N)
+    free = np.repeat((g > 0)[None, :], B, axis=0)
+    for b, s in enumerate(sets):
+        free[b, list(s)] = False
+    info = np.zeros(B, np.int32)
+    if status is not None:
+        info[np.asarray(status).reshape(B) != 0] = NOT_CONVERGED
+    with np.errstate(all="ignore"):
+        a, l, da, dl, u, v = _np_parts(ws, bs, wp, bp, y)
+    acc, cnt = np.zeros((K, N), dt), np.zeros(K, dt)
+    eye, at = np.eye(2 * H), np.arange(K)
+    for b in np.nonzero(info == 0)[0]:
+        mb = free[b].astype(dt)
+        C = np.concatenate([ws * da[b][None, :], v[b][:, None] * wp * dl[b][None, :]], axis=0)
+        A = eye - ((C * mb[None, :]) @ wa).astype(np.float64)
+        try:
+            if not np.all(np.isfinite(A)):
+                raise np.linalg.LinAlgError
+            Z = np.linalg.inv(A)
+        except np.linalg.LinAlgError:
+            info[b] = 1
+            continue
+        if not np.all(np.isfinite(Z)):
+            info[b] = -1
+            continue
+        with np.errstate(all="ignore"):
+            X = Z.astype(dt) @ C[:, regs]                                # [2H, K]
+            d = 1 + mb[regs] * np.einsum("kc,ck->k", wa[regs], X)
+            ok = np.isfinite(d) & (d != 0)
+            T = mb[:, None] * (wa @ X)                                   # [N, K]: target j, regulator k
+            if input == "production":
+                R = T * mb[regs][None, :]
+                R[regs, at] += mb[regs]
+            else:
+                R = T / np.where(ok, d, 1)[None, :]
+                R[regs, at] = 0
+            R[:, ~ok] = 0
+        acc += np.abs(R.T) if reduce == "mean_abs" else R.T
+        cnt += ok
+    response = acc / np.where(cnt > 0, cnt, 1)[:, None]
+    if input == "level":
+        response[at, regs] = cnt > 0
+    return SteadyResponse(regs, response, _response_scores(response, regs, N, np), info)
