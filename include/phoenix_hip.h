@@ -690,7 +690,7 @@ int phx_reduced_jacobian(const phx_params *p, const float *y, const float *m, co
  * phx_steady_residual: hid [B, 2H] as above and r [B, N] = Wa hid - y (c ascending per gene).
  * phx_steady_update:   out [B, N] = y + m (r + Wa x) where m != 0, y (to the bit) where m == 0; x [B, 2H].
  * phx_steady_solve:    (I - S_b) x_b = w_b in double, LU with partial pivoting, one workgroup per state; x [B, 2H] float,
- *   info [B] = 0, k + 1 where column k has no finite non-zero pivot, -1 where the solution is not finite (x_b = 0 then).
+ *   info [B] = 0, k + 1 where column k has no finite non-zero pivot, -1 where the solution is not finite as float (x_b = 0 for both).
  *   workspace: phx_steady_solve_workspace_bytes(H, B) = B (2H)^2 doubles.
  * PHX_ERR_BAD_ARG before any device call for a null pointer or a shape outside the ranges, PHX_ERR_WORKSPACE as above. */
 int phx_steady_residual(const phx_params *p, const float *y, int B, float *hid, float *r, void *stream);
@@ -745,7 +745,7 @@ int phx_steady_param_grads(const phx_params *p, const float *y, const float *lam
  * device, float unless said otherwise.
  * phx_steady_inverse: Z [B, 2H, 2H] float = (I - S_b)^-1, computed in double by LU with partial pivoting on [I - S | I],
  *   one workgroup per state, the pivot rule and the info codes of phx_steady_solve (0; k + 1: column k has no finite
- *   non-zero pivot; -1: the inverse is not finite; Z_b = 0 for both).  Workspace: phx_steady_inverse_workspace_bytes(H, B)
+ *   non-zero pivot; -1: the inverse is not finite as float; Z_b = 0 for both).  Workspace: phx_steady_inverse_workspace_bytes(H, B)
  *   = 2 B (2H)^2 doubles.
  * phx_steady_response_factors: for the K regulators genes[k] (int, 0 <= gene < N, device) and every state the column
  *   x_bk = Z_b C_b[:, gene] = a'(y) (Z_b[:, :H] Ws[:, gene]) + l'(y) ((Z_b[:, H:] diag hid_b[H:]) Wp[:, gene]), y = y[b, gene]:

@@ -304,8 +304,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_st_wa(const float *__restrict__ 
 
 // (I - S_b) x = w_b in double, LU with partial pivoting (the first row of the largest magnitude), one workgroup of sixteen
 // waves per state; A [B][n][n] doubles of workspace.  info[b] = 0, or k + 1 where column k has no finite non-zero pivot, or
-// -1 where the solution is not finite; x of such a state is zero.  Every entry is updated by one thread in an order fixed
-// by n alone.
+// -1 where the solution is not finite as float (an entry beyond the float range counts, as the result is stored as
+// float); x of such a state is zero.  Every entry is updated by one thread in an order fixed by n alone.
 __global__ __launch_bounds__(LU_THREADS) void k_st_solve(const float *__restrict__ S, const float *__restrict__ w, int n,
                                                          double *__restrict__ Aall, float *__restrict__ x, int *__restrict__ info)
 {
@@ -397,7 +397,7 @@ __global__ __launch_bounds__(LU_THREADS) void k_st_solve(const float *__restrict
             __syncthreads();
         }
         int nf = 0;
-        for (int i = tid; i < n; i += LU_THREADS) nf |= !(fabs(rhs[i]) <= 1.7976931348623157e308);
+        for (int i = tid; i < n; i += LU_THREADS) nf |= !(fabsf((float)rhs[i]) <= 3.4028234663852886e38f);       // as it is stored
         if (__syncthreads_or(nf)) bad = -1;
     }
     for (int i = tid; i < n; i += LU_THREADS) x[(size_t)b * n + i] = bad ? 0.f : (float)rhs[i];

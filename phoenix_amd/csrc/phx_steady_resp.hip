@@ -66,7 +66,8 @@ __device__ __forceinline__ f4 ld4(const float *src, int nv)
 }
 
 // Z_b = (I - S_b)^-1.  A [B][n][2n] doubles of workspace: [I - S | I], eliminated in place; info[b] = 0, or k + 1 where
-// column k has no finite non-zero pivot, or -1 where the inverse is not finite; Z of such a state is zero.
+// column k has no finite non-zero pivot, or -1 where the inverse is not finite as float (an entry beyond the float range
+// counts, as the result is stored as float); Z of such a state is zero.
 __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restrict__ S, int n, double *__restrict__ Aall,
                                                             float *__restrict__ Z, int *__restrict__ info)
 {
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restr
         int nf = 0;
         for (int idx = tid; idx < n * n; idx += INV_THREADS) {
             const int i = idx / n, j = idx - i * n;
-            nf |= !(fabs(A[(size_t)i * n2 + n + j]) <= DBL_BIG);
+            nf |= !(fabsf((float)A[(size_t)i * n2 + n + j]) <= 3.4028234663852886e38f);       // as it is stored
         }
         if (__syncthreads_or(nf)) bad = -1;
     }

@@ -1465,7 +1465,15 @@ def steady_update(p, y, m, r, x):
 
 
 def steady_solve(S, w):
-    """(x [B, n] float32, info [B] int32) of (I - S_b) x_b = w_b, solved in float64 on the device: phx_steady_solve"""
+    """(x [B, n] float32, info [B] int32) of (I - S_b) x_b = w_b, solved in float64 on the device: phx_steady_solve.  S
+    [B, n, n] and w [B, n] float32 on one device, n even; a view (a transpose, say) is solved as the matrix it shows."""
+    _require_gpu(S, "S")
+    _require_gpu(w, "w")
+    if S.dim() != 3 or S.shape[1] != S.shape[2] or S.shape[1] % 2 or S.shape[0] < 1:
+        raise ValueError("steady_solve: S must be [B, 2H, 2H], got %s" % (tuple(S.shape),))
+    if tuple(w.shape) != tuple(S.shape[:2]) or w.device != S.device:
+        raise ValueError("steady_solve: w must be %s on the device of S, got %s" % (tuple(S.shape[:2]), tuple(w.shape)))
+    S, w = S.detach().contiguous(), w.detach().contiguous()
     B, n = w.shape
     x = torch.empty_like(w)
     info = torch.empty(B, dtype=torch.int32, device=w.device)
