@@ -9,12 +9,12 @@
 //                 Ws (sums branch) and of Wp (products branch); the B operand is the N x (2H + 2) block
 //                 [diag(d m) WaT^T | act | d m r] with (act, d) = (a, a') or (l, l').  A workgroup (256 threads, four waves
 //                 of 32 x 32 outputs) owns a 64 x 64 block of one branch's H x (2H + 2) outputs, a segment of the gene axis
-//                 and a group of RJ_SB = 4 states.  It walks its segment RJ_KC = 32 genes at a time: the chunk's 64 rows of
-//                 the branch's weights and 64 rows of WaT lie in LDS (rows of 34 floats: the ds_read_b32 of an MFMA operand,
-//                 lane (lc, lq) at row lc, float lq, meets 32 distinct banks per half wave) and stay there while the
-//                 workgroup walks its states; the state's three per-gene vectors lie beside them, and the B operand is the
-//                 WaT entry times the vector of the lane's column (the last two columns hold 1.0 in the panel), formed as
-//                 it is read.  v_mfma_f32_16x16x4_f32, K ascending.  A 16 x 16 tile outside the matrix is not computed.
+//                 and a group of RJ_SB = 4 states.  It walks its segment TILE_KC = 32 genes at a time: the chunk's 64 rows of
+//                 the branch's weights and 64 rows of WaT lie in LDS (the row-major panels of phx_steady_tile.inc, which
+//                 holds what the tile kernels of the family share) and stay there while the workgroup walks its states;
+//                 the state's three per-gene vectors lie beside them, and the B operand is the WaT entry times the vector
+//                 of the lane's column (the last two columns hold 1.0 in the panel), formed as it is read.
+//                 v_mfma_f32_16x16x4_f32, K ascending.  A 16 x 16 tile outside the matrix is not computed.
 //   k_rj_finish   adds the segments' partial blocks in segment order, adds the bias (and takes exp) for the hidden vector,
 //                 and scales the product rows of S and w by v_j afterwards.
 //   sum order     entry (j, c) of a state: per segment the fmaf chain of the MFMA over the segment's genes ascending (four
@@ -24,7 +24,8 @@
 //   k_st_hidden, k_st_wa, k_st_solve   the RHS-sized passes and the dense solve of the iteration, each in an order fixed by
 //                 the shape alone: the hidden vector of a state (one workgroup per four hidden rows), out = x WaT with the
 //                 residual or the update fused (c ascending, one thread per gene), and (I - S) x = w in double by LU with
-//                 partial pivoting, one workgroup per state.
+//                 partial pivoting, one workgroup per state, by the rule and the steps that phx_dense_lu.inc describes
+//                 (k_sr_inverse, phx_steady_resp.hip, calls them; this kernel keeps them written out, see there).
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -35,22 +36,14 @@
 
 namespace {
 
-constexpr int RJ_T = 64;              // rows and columns of a workgroup's block
-constexpr int RJ_KC = 32;             // genes of a staged chunk
-constexpr int RJ_LD = RJ_KC + 2;      // floats of a panel row
+#include "phx_dense_lu.inc"
+#include "phx_steady_tile.inc"
+
 constexpr int RJ_SB = 4;              // states of a workgroup
-constexpr int RJ_THREADS = 256;
-constexpr int RJ_MAX_H = 256;
 constexpr int RJ_WGS = 256;           // workgroups of one group of states that the segment count aims at
 constexpr size_t RJ_WS_CAP = (size_t)64 << 20;   // bytes of partial blocks per launch: more states are walked in chunks
-constexpr int ST_THREADS = 256;
 constexpr int ST_ROWS = 4;            // hidden rows of a workgroup of k_st_hidden
 constexpr int LU_THREADS = 1024;      // threads of a workgroup of k_st_solve
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 struct rj_geom {
     int RB, CB, nblk, NC, T, S;
@@ -60,10 +53,10 @@ __host__ __device__ inline rj_geom rj_geometry(int N, int H)
 {
     rj_geom q;
     q.NC = 2 * H + 2;
-    q.RB = (H + RJ_T - 1) / RJ_T;
-    q.CB = (q.NC + RJ_T - 1) / RJ_T;
+    q.RB = (H + TILE - 1) / TILE;
+    q.CB = (q.NC + TILE - 1) / TILE;
     q.nblk = 2 * q.RB * q.CB;
-    q.T = (N + RJ_KC - 1) / RJ_KC;
+    q.T = (N + TILE_KC - 1) / TILE_KC;
     const int want = (RJ_WGS + q.nblk - 1) / q.nblk;
     q.S = want < q.T ? want : q.T;
     return q;
@@ -75,17 +68,19 @@ struct rj_args {
     int B;
 };
 
-// acc[ti][tj] += A(rows of tile ti) x B(columns of tile tj) over the chunk; NI, NJ: the wave's tiles inside the matrix
+// acc[ti][tj] += A(rows of tile ti) x B(columns of tile tj) over the chunk; NI, NJ: the wave's tiles inside the matrix.
+// Not tile_kloop: the B operand is scaled by the state's vector as it is read, and the tile counts are template arguments
+// because the loop runs once per state of the group on the same staged chunk.
 template <int NI, int NJ>
 __device__ __forceinline__ void rj_kloop(const float *pa, const float *pb, const float *v0, const float *v1, f4 (&acc)[2][2])
 {
 #pragma unroll
-    for (int kk = 0; kk < RJ_KC / 4; ++kk) {
+    for (int kk = 0; kk < TILE_KC / 4; ++kk) {
         float a[2], b[2];
 #pragma unroll
-        for (int ti = 0; ti < NI; ++ti) a[ti] = pa[ti * 16 * RJ_LD + 4 * kk];
+        for (int ti = 0; ti < NI; ++ti) a[ti] = pa[ti * 16 * TILE_LD + 4 * kk];
         b[0] = pb[4 * kk] * v0[4 * kk];
-        if (NJ > 1) b[1] = pb[16 * RJ_LD + 4 * kk] * v1[4 * kk];
+        if (NJ > 1) b[1] = pb[16 * TILE_LD + 4 * kk] * v1[4 * kk];
 #pragma unroll
         for (int ti = 0; ti < NI; ++ti)
 #pragma unroll
@@ -93,31 +88,30 @@ __device__ __forceinline__ void rj_kloop(const float *pa, const float *pb, const
     }
 }
 
-__global__ __launch_bounds__(RJ_THREADS) void k_rj(const float *__restrict__ Ws, const float *__restrict__ Wp,
+__global__ __launch_bounds__(ST_THREADS) void k_rj(const float *__restrict__ Ws, const float *__restrict__ Wp,
                                                    const float *__restrict__ WaT, int N, int H, rj_args a)
 {
-    __shared__ float pa_s[RJ_T * RJ_LD], pb_s[RJ_T * RJ_LD], vec[RJ_SB * 3 * RJ_KC];
-    const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int iw = (wv & 1) * 32, jw = (wv >> 1) * 32;
+    __shared__ float pa_s[TILE * TILE_LD], pb_s[TILE * TILE_LD], vec[RJ_SB * 3 * TILE_KC];
+    const tile_lane L = tile_lanes();
+    const int tid = L.tid;
     const rj_geom q = rj_geometry(N, H);
     const int blk = blockIdx.x % q.nblk, rest = blockIdx.x / q.nblk;
     const int seg = rest % q.S, sg = rest / q.S;
     const int br = blk / (q.RB * q.CB), rb = (blk - br * q.RB * q.CB) / q.CB, cb = blk % q.CB;
-    const int row0 = rb * RJ_T, col0 = cb * RJ_T, H2 = 2 * H;
+    const int row0 = rb * TILE, col0 = cb * TILE, H2 = 2 * H;
     const float *W = br ? Wp : Ws;
     const int b0 = sg * RJ_SB, nb = min(RJ_SB, a.B - b0);
-    const int t_begin = (int)((long long)seg * q.T / q.S), t_end = (int)((long long)(seg + 1) * q.T / q.S);
-    // the wave's tiles inside the matrix (uniform over the wave)
-    const int ni = min(2, max(0, (H - (row0 + iw) + 15) / 16)), nj = min(2, max(0, (q.NC - (col0 + jw) + 15) / 16));
+    int t_begin, t_end;
+    seg_range(seg, q.T, q.S, t_begin, t_end);
+    const int ni = tiles_inside(H, row0 + L.iw), nj = tiles_inside(q.NC, col0 + L.jw);
     // which of the state's vectors scales this lane's column of tile tj: d m, act (column 2H) or d m r (column 2H + 1)
     int which[2];
 #pragma unroll
     for (int tj = 0; tj < 2; ++tj) {
-        const int c = col0 + jw + 16 * tj + lc;
+        const int c = col0 + L.jw + 16 * tj + L.lc;
         which[tj] = c < H2 ? 0 : (c == H2 ? 1 : 2);
     }
-    const float *pa = pa_s + (iw + lc) * RJ_LD + lq, *pb = pb_s + (jw + lc) * RJ_LD + lq;
+    const float *pa = pa_s + (L.iw + L.lc) * TILE_LD + L.lq, *pb = pb_s + (L.jw + L.lc) * TILE_LD + L.lq;
 
     const f4 zero = {0.f, 0.f, 0.f, 0.f};
     f4 acc[RJ_SB][2][2];
@@ -129,41 +123,29 @@ __global__ __launch_bounds__(RJ_THREADS) void k_rj(const float *__restrict__ Ws,
             for (int tj = 0; tj < 2; ++tj) acc[st][ti][tj] = zero;
 
     for (int t = t_begin; t < t_end; ++t) {
-        const int n0 = t * RJ_KC;
+        const int n0 = t * TILE_KC;
         __syncthreads();                       // every wave is done with the previous chunk
         // the panels: 64 rows of 32 genes each, a quad of genes per thread and step; zeros outside the matrices
 #pragma unroll
-        for (int u = 0; u < 2 * RJ_T * RJ_KC / 4 / RJ_THREADS; ++u) {
-            const int idx = tid + u * RJ_THREADS, panel = idx >> 9, rr = (idx >> 3) & 63, c4 = (idx & 7) * 4, n = n0 + c4;
-            f4 v = zero;
-            if (n < N) {
-                const float *src = nullptr;
-                if (panel == 0) {
-                    if (row0 + rr < H) src = W + (size_t)(row0 + rr) * N + n;
-                } else if (col0 + rr < H2) {
-                    src = WaT + (size_t)(col0 + rr) * N + n;
-                }
-                if (src) {
-                    if (n + 3 < N) {
-                        __builtin_memcpy(&v, src, sizeof(f4));
-                    } else {
-                        v[0] = src[0];
-                        if (n + 1 < N) v[1] = src[1];
-                        if (n + 2 < N) v[2] = src[2];
-                    }
-                } else if (panel == 1 && col0 + rr < q.NC) {        // the columns of act and of d m r
-                    v[0] = 1.f;
-                    if (n + 1 < N) v[1] = 1.f;
-                    if (n + 2 < N) v[2] = 1.f;
-                    if (n + 3 < N) v[3] = 1.f;
-                }
+        for (int u = 0; u < 2 * TILE * TILE_KC / 4 / ST_THREADS; ++u) {
+            const tile_quad s = tile_quad_at(tid + u * ST_THREADS);
+            const int n = n0 + s.c4, row = (s.panel ? col0 : row0) + s.rr;
+            const float *src = nullptr;
+            if (s.panel == 0) {
+                if (row < H) src = W + (size_t)row * N + n;
+            } else if (row < H2) {
+                src = WaT + (size_t)row * N + n;
             }
-            float *dst = (panel ? pb_s : pa_s) + rr * RJ_LD + c4;   // 8-byte aligned
-            *reinterpret_cast<f2 *>(dst) = (f2){v[0], v[1]};
-            *reinterpret_cast<f2 *>(dst + 2) = (f2){v[2], v[3]};
+            f4 v = ld4(src, src ? N - n : 0);          // n may lie past the row's end: ld4 reads nothing where nv <= 0
+            if (s.panel == 1 && row >= H2 && row < q.NC) {          // the columns of act and of d m r
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (n + e < N) v[e] = 1.f;
+            }
+            st4((s.panel ? pb_s : pa_s) + s.rr * TILE_LD + s.c4, v);
         }
         // the states' vectors of the chunk: thread (st, kk)
-        if (tid < RJ_SB * RJ_KC) {
+        if (tid < RJ_SB * TILE_KC) {
             const int st = tid >> 5, kk = tid & 31, n = n0 + kk;
             float dm = 0.f, av = 0.f, dmr = 0.f;
             if (st < nb && n < N) {
@@ -178,16 +160,16 @@ __global__ __launch_bounds__(RJ_THREADS) void k_rj(const float *__restrict__ Ws,
                     if (a.r) dmr = dm * a.r[at];
                 }
             }
-            vec[(st * 3 + 0) * RJ_KC + kk] = dm;
-            vec[(st * 3 + 1) * RJ_KC + kk] = av;
-            vec[(st * 3 + 2) * RJ_KC + kk] = dmr;
+            vec[(st * 3 + 0) * TILE_KC + kk] = dm;
+            vec[(st * 3 + 1) * TILE_KC + kk] = av;
+            vec[(st * 3 + 2) * TILE_KC + kk] = dmr;
         }
         __syncthreads();
         if (ni > 0 && nj > 0) {
 #pragma unroll
             for (int st = 0; st < RJ_SB; ++st) {
                 if (st < nb) {
-                    const float *v0 = vec + (st * 3 + which[0]) * RJ_KC + lq, *v1 = vec + (st * 3 + which[1]) * RJ_KC + lq;
+                    const float *v0 = vec + (st * 3 + which[0]) * TILE_KC + L.lq, *v1 = vec + (st * 3 + which[1]) * TILE_KC + L.lq;
                     if (ni == 2 && nj == 2) rj_kloop<2, 2>(pa, pb, v0, v1, acc[st]);
                     else if (ni == 2) rj_kloop<2, 1>(pa, pb, v0, v1, acc[st]);
                     else if (nj == 2) rj_kloop<1, 2>(pa, pb, v0, v1, acc[st]);
@@ -206,10 +188,10 @@ __global__ __launch_bounds__(RJ_THREADS) void k_rj(const float *__restrict__ Ws,
         for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
             for (int tj = 0; tj < 2; ++tj) {
-                const int c = col0 + jw + 16 * tj + lc;
+                const int c = col0 + L.jw + 16 * tj + L.lc;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int row = row0 + iw + 16 * ti + 4 * lq + r;
+                    const int row = row0 + L.iw + 16 * ti + 4 * L.lq + r;
                     if (row < H && c < q.NC) out[(size_t)row * q.NC + c] = acc[st][ti][tj][r];
                 }
             }
@@ -225,20 +207,17 @@ __global__ __launch_bounds__(128) void k_rj_finish(const float *__restrict__ par
     const int H2 = 2 * H, b = blockIdx.x / H2, j = blockIdx.x - b * H2;
     const size_t stride = (size_t)B * H2 * NC;
     const float *base = part + ((size_t)b * H2 + j) * NC;
-    float hs = base[H2];
-    for (int s = 1; s < S; ++s) hs += base[s * stride + H2];
+    const float hs = seg_sum(base + H2, S, stride);
     const bool prod = j >= H;
     const float hv = prod ? expf(hs + bp[j - H]) : hs + bs[j];
     for (int c = threadIdx.x; c < H2; c += 128) {
-        float s = base[c];
-        for (int k = 1; k < S; ++k) s += base[k * stride + c];
+        const float s = seg_sum(base + c, S, stride);
         Sout[((size_t)b * H2 + j) * H2 + c] = prod ? hv * s : s;
     }
     if (threadIdx.x == 0) {
         hid[(size_t)b * H2 + j] = hv;
         if (w) {
-            float s = base[H2 + 1];
-            for (int k = 1; k < S; ++k) s += base[k * stride + H2 + 1];
+            const float s = seg_sum(base + H2 + 1, S, stride);
             w[(size_t)b * H2 + j] = prod ? hv * s : s;
         }
     }
@@ -286,7 +265,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_st_wa(const float *__restrict__ 
                                                       const float *__restrict__ y, const float *__restrict__ m,
                                                       const float *__restrict__ r, int update, float *__restrict__ out)
 {
-    __shared__ float xs[2 * RJ_MAX_H];
+    __shared__ float xs[2 * STEADY_MAX_H];
     const int b = blockIdx.y, n = blockIdx.x * ST_THREADS + threadIdx.x;
     for (int c = threadIdx.x; c < H2; c += ST_THREADS) xs[c] = x[(size_t)b * H2 + c];
     __syncthreads();
@@ -306,11 +285,14 @@ __global__ __launch_bounds__(ST_THREADS) void k_st_wa(const float *__restrict__ 
 // waves per state; A [B][n][n] doubles of workspace.  info[b] = 0, or k + 1 where column k has no finite non-zero pivot, or
 // -1 where the solution is not finite as float (an entry beyond the float range counts, as the result is stored as
 // float); x of such a state is zero.  Every entry is updated by one thread in an order fixed by n alone.
+// The steps are written out here, not called from phx_dense_lu.inc: in one timing of whole-kernel builds (24 states,
+// n = 400) every build that called one or more of the shared steps ran 0.15 % to 0.6 % slower, this one 0.07 %, against a
+// spread of 0.1 % between runs.  That is no cost of a single step.  A change of the pivot rule is made here and there.
 __global__ __launch_bounds__(LU_THREADS) void k_st_solve(const float *__restrict__ S, const float *__restrict__ w, int n,
                                                          double *__restrict__ Aall, float *__restrict__ x, int *__restrict__ info)
 {
     constexpr int NW = LU_THREADS / 64;
-    __shared__ double rhs[2 * RJ_MAX_H], lcol[2 * RJ_MAX_H], rv[NW];
+    __shared__ double rhs[2 * STEADY_MAX_H], lcol[2 * STEADY_MAX_H], rv[NW];
     __shared__ int ri[NW];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     double *A = Aall + (size_t)b * n * n;
@@ -323,12 +305,12 @@ __global__ __launch_bounds__(LU_THREADS) void k_st_solve(const float *__restrict
     __syncthreads();
     int bad = 0;
     for (int k = 0; k < n; ++k) {
-        // the pivot: largest |A[i][k]| over i >= k, the smallest i among equals; a non-finite entry wins and ends the solve
+        // the pivot, by the rule of phx_dense_lu.inc; a non-finite entry wins and ends the solve
         double best = -1.0;
         int bi = k;
         for (int i = k + tid; i < n; i += LU_THREADS) {
             double v = fabs(A[(size_t)i * n + k]);
-            if (!(v <= 1.7976931348623157e308)) v = __builtin_huge_val();       // NaN or Inf
+            if (!(v <= LU_DBL_MAX)) v = __builtin_huge_val();       // NaN or Inf
             if (v > best) {
                 best = v;
                 bi = i;
@@ -397,16 +379,16 @@ __global__ __launch_bounds__(LU_THREADS) void k_st_solve(const float *__restrict
             __syncthreads();
         }
         int nf = 0;
-        for (int i = tid; i < n; i += LU_THREADS) nf |= !(fabsf((float)rhs[i]) <= 3.4028234663852886e38f);       // as it is stored
+        for (int i = tid; i < n; i += LU_THREADS) nf |= !finite_as_float(rhs[i]);
         if (__syncthreads_or(nf)) bad = -1;
     }
     for (int i = tid; i < n; i += LU_THREADS) x[(size_t)b * n + i] = bad ? 0.f : (float)rhs[i];
     if (tid == 0) info[b] = bad;
 }
 
-bool rj_params_ok(const phx_params *p)
+bool rj_params_ok(const phx_params *p, int B)
 {
-    return p && p->Ws && p->bs && p->Wp && p->bp && p->WaT && p->N >= 1 && p->H >= 1 && p->H <= RJ_MAX_H;
+    return steady_shape_ok(p, B) && p->Ws && p->bs && p->Wp && p->bp && p->WaT;
 }
 
 // states of one launch: all of them while their partial blocks stay under RJ_WS_CAP, else a multiple of RJ_SB
@@ -419,15 +401,13 @@ int rj_chunk(int N, int H, int B)
     return (size_t)B < fit ? B : (int)fit;
 }
 
-bool launched() { return hipGetLastError() == hipSuccess; }
-
 }  // namespace
 
 extern "C" {
 
 size_t phx_reduced_jacobian_workspace_bytes(int N, int H, int B)
 {
-    if (N < 1 || H < 1 || H > RJ_MAX_H || B < 1) return 0;
+    if (!steady_shape_ok(N, H, B)) return 0;
     const rj_geom q = rj_geometry(N, H);
     return (size_t)q.S * rj_chunk(N, H, B) * 2 * H * q.NC * sizeof(float);
 }
@@ -435,7 +415,7 @@ size_t phx_reduced_jacobian_workspace_bytes(int N, int H, int B)
 int phx_reduced_jacobian(const phx_params *p, const float *y, const float *m, const float *r, int B, float *S, float *w,
                          float *hid, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!rj_params_ok(p) || !y || !m || !S || !hid || B < 1) return PHX_ERR_BAD_ARG;
+    if (!rj_params_ok(p, B) || !y || !m || !S || !hid) return PHX_ERR_BAD_ARG;
     if ((r != nullptr) != (w != nullptr)) return PHX_ERR_BAD_ARG;       // w is written exactly where r is given
     const int N = p->N, H = p->H, H2 = 2 * H;
     if (!workspace || workspace_bytes < phx_reduced_jacobian_workspace_bytes(N, H, B)) return PHX_ERR_WORKSPACE;
@@ -451,7 +431,7 @@ int phx_reduced_jacobian(const phx_params *p, const float *y, const float *m, co
         a.part = static_cast<float *>(workspace);
         a.B = nb;
         const int groups = (nb + RJ_SB - 1) / RJ_SB;
-        hipLaunchKernelGGL(k_rj, dim3((unsigned)(groups * q.S * q.nblk)), dim3(RJ_THREADS), 0, st, p->Ws, p->Wp, p->WaT, N, H, a);
+        hipLaunchKernelGGL(k_rj, dim3((unsigned)(groups * q.S * q.nblk)), dim3(ST_THREADS), 0, st, p->Ws, p->Wp, p->WaT, N, H, a);
         if (!launched()) return PHX_ERR_LAUNCH;
         hipLaunchKernelGGL(k_rj_finish, dim3((unsigned)(nb * H2)), dim3(128), 0, st, a.part, p->bs, p->bp, H, q.NC, q.S, nb,
                            S + (size_t)b0 * H2 * H2, w ? w + (size_t)b0 * H2 : nullptr, hid + (size_t)b0 * H2);
@@ -462,7 +442,7 @@ int phx_reduced_jacobian(const phx_params *p, const float *y, const float *m, co
 
 int phx_steady_residual(const phx_params *p, const float *y, int B, float *hid, float *r, void *stream)
 {
-    if (!rj_params_ok(p) || !y || !hid || !r || B < 1 || B > 65535) return PHX_ERR_BAD_ARG;
+    if (!rj_params_ok(p, B) || !y || !hid || !r || B > 65535) return PHX_ERR_BAD_ARG;
     const int N = p->N, H = p->H, H2 = 2 * H;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_st_hidden, dim3((unsigned)((H2 + ST_ROWS - 1) / ST_ROWS), (unsigned)B), dim3(ST_THREADS), 0, st, p->Ws,
@@ -476,8 +456,7 @@ int phx_steady_residual(const phx_params *p, const float *y, int B, float *hid, 
 int phx_steady_update(const phx_params *p, const float *y, const float *m, const float *r, const float *x, int B, float *out,
                       void *stream)
 {
-    if (!p || !p->WaT || p->N < 1 || p->H < 1 || p->H > RJ_MAX_H || !y || !m || !r || !x || !out || B < 1 || B > 65535)
-        return PHX_ERR_BAD_ARG;
+    if (!steady_shape_ok(p, B) || !p->WaT || !y || !m || !r || !x || !out || B > 65535) return PHX_ERR_BAD_ARG;
     hipLaunchKernelGGL(k_st_wa, dim3((unsigned)((p->N + ST_THREADS - 1) / ST_THREADS), (unsigned)B), dim3(ST_THREADS), 0,
                        (hipStream_t)stream, p->WaT, p->N, 2 * p->H, x, y, m, r, 1, out);
     return launched() ? PHX_OK : PHX_ERR_LAUNCH;
@@ -485,14 +464,14 @@ int phx_steady_update(const phx_params *p, const float *y, const float *m, const
 
 size_t phx_steady_solve_workspace_bytes(int H, int B)
 {
-    if (H < 1 || H > RJ_MAX_H || B < 1) return 0;
+    if (!steady_shape_ok(/* N */ 1, H, B)) return 0;
     return (size_t)B * 4 * H * H * sizeof(double);
 }
 
 int phx_steady_solve(const float *S, const float *w, int H, int B, float *x, int *info, void *workspace, size_t workspace_bytes,
                      void *stream)
 {
-    if (!S || !w || !x || !info || H < 1 || H > RJ_MAX_H || B < 1) return PHX_ERR_BAD_ARG;
+    if (!S || !w || !x || !info || !steady_shape_ok(/* N */ 1, H, B)) return PHX_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < phx_steady_solve_workspace_bytes(H, B)) return PHX_ERR_WORKSPACE;
     hipLaunchKernelGGL(k_st_solve, dim3((unsigned)B), dim3(LU_THREADS), 0, (hipStream_t)stream, S, w, 2 * H,
                        static_cast<double *>(workspace), x, info);

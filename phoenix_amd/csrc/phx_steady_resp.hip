@@ -5,9 +5,9 @@
 // Holding gene k and moving its level gives dy / d(level k) = R[:, k] / R[k, k].
 //
 //   k_sr_inverse    Z_b in double: LU with partial pivoting on [I - S_b | I], one workgroup of sixteen waves per state, the
-//                   pivot rule and the info codes of k_st_solve (phx_steady.hip, which is untouched); back substitution of
-//                   the n right-hand sides a row at a time.  Every entry is updated by one thread per step, in an order
-//                   fixed by n alone.
+//                   steps (phx_dense_lu.inc), the pivot rule and the info codes of k_st_solve (phx_steady.hip); back
+//                   substitution of the n right-hand sides a row at a time.  Every entry is updated by one thread per
+//                   step, in an order fixed by n alone.
 //   k_sr_factors    x_bk = Z_b C_b[:, gene k] before its scaling: a per-state contraction over the hidden index,
 //                   v_mfma_f32_16x16x4_f32, a wave owns 16 rows of Z x 64 regulators; A operand Z_b[c, j] (second half:
 //                   times v_bj), B operand Ws[j, gene] / Wp[j, gene] straight from the engine layout (K-major); the two
@@ -16,8 +16,8 @@
 //                   (production) or divided by d_bk (level); zeros and use = 0 where the row is left out.
 //   k_sr_response   the hot kernel.  A workgroup (256 threads, four waves of 32 x 32 outputs) owns 64 regulators x 64
 //                   targets in accumulators for the whole loop over the states.  It walks (state, 32 rows of the 2H) steps:
-//                   the X chunk of a step lies in one half of a double buffer in LDS (rows of 80 floats: the ds_read_b32 of
-//                   an operand, lane (lc, lq) at float 80 lq + lc, meets 32 distinct banks per half wave), the chunk of the
+//                   the X chunk of a step lies in one half of a double buffer in LDS (the K-major panels and the K loop of
+//                   phx_steady_tile.inc), the chunk of the
 //                   NEXT step is requested from global memory before the products of this one and stored behind them: one
 //                   barrier per step.  The WaT panel of the tile's targets does not depend on the state: it is loaded once
 //                   and stays in LDS where the workgroup stays within 64 KiB (2H <= 128: two workgroups and more per CU),
@@ -37,33 +37,12 @@
 
 namespace {
 
-constexpr int SR_MAX_H = 256;
+#include "phx_dense_lu.inc"
+#include "phx_steady_tile.inc"
+
 constexpr int INV_THREADS = 1024;     // threads of a workgroup of k_sr_inverse
-constexpr int SR_THREADS = 256;
-constexpr int SR_T = 64;              // regulators and targets of a workgroup's tile
-constexpr int SR_KC = 32;             // rows of a staged chunk
-constexpr int SR_LD = 80;             // floats of a chunk row in LDS
-constexpr int SR_CHUNK = SR_KC * SR_LD;
+constexpr int SR_CHUNK = TILE_KC * TILE_LDK;      // floats of a staged chunk
 constexpr int SR_RES_CHUNKS = 4;      // the WaT panel stays in LDS up to this many chunks (2H <= 128)
-constexpr double DBL_BIG = 1.7976931348623157e308;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// the first nv (0 .. 4) floats at src, zeros behind them; src is not read where nv == 0
-__device__ __forceinline__ f4 ld4(const float *src, int nv)
-{
-    f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (nv >= 4) {
-        __builtin_memcpy(&v, src, sizeof(f4));
-    } else if (nv > 0) {
-        v[0] = src[0];
-        if (nv > 1) v[1] = src[1];
-        if (nv > 2) v[2] = src[2];
-    }
-    return v;
-}
 
 // Z_b = (I - S_b)^-1.  A [B][n][2n] doubles of workspace: [I - S | I], eliminated in place; info[b] = 0, or k + 1 where
 // column k has no finite non-zero pivot, or -1 where the inverse is not finite as float (an entry beyond the float range
@@ -72,9 +51,9 @@ __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restr
                                                             float *__restrict__ Z, int *__restrict__ info)
 {
     constexpr int NW = INV_THREADS / 64;
-    __shared__ double lcol[2 * SR_MAX_H], rv[NW];
+    __shared__ double lcol[2 * STEADY_MAX_H], rv[NW];
     __shared__ int ri[NW];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n2 = 2 * n;
+    const int b = blockIdx.x, tid = threadIdx.x, n2 = 2 * n;
     double *A = Aall + (size_t)b * n * n2;
     const float *Sb = S + (size_t)b * n * n;
     for (int idx = tid; idx < n * n2; idx += INV_THREADS) {
@@ -84,60 +63,17 @@ __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restr
     __syncthreads();
     int bad = 0;
     for (int k = 0; k < n; ++k) {
-        // the pivot: largest |A[i][k]| over i >= k, the smallest i among equals; a non-finite entry wins and ends the state
-        double best = -1.0;
-        int bi = k;
-        for (int i = k + tid; i < n; i += INV_THREADS) {
-            double v = fabs(A[(size_t)i * n2 + k]);
-            if (!(v <= DBL_BIG)) v = __builtin_huge_val();       // NaN or Inf
-            if (v > best) {
-                best = v;
-                bi = i;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(best, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (o > best || (o == best && oi < bi)) {
-                best = o;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            rv[wv] = best;
-            ri[wv] = bi;
-        }
-        __syncthreads();
-        double pmax = rv[0];
-        int piv = ri[0];
-#pragma unroll
-        for (int q = 1; q < NW; ++q)
-            if (rv[q] > pmax || (rv[q] == pmax && ri[q] < piv)) {
-                pmax = rv[q];
-                piv = ri[q];
-            }
-        if (!(pmax > 0.0) || pmax == __builtin_huge_val()) {      // uniform over the workgroup
+        int piv;
+        if (!pivot<INV_THREADS>(A, n2, n, k, rv, ri, piv)) {      // a non-finite entry wins and ends the state
             bad = k + 1;
             break;
         }
-        if (piv != k) {
-            for (int j = k + tid; j < n2; j += INV_THREADS) {
-                const double t = A[(size_t)k * n2 + j];
-                A[(size_t)k * n2 + j] = A[(size_t)piv * n2 + j];
-                A[(size_t)piv * n2 + j] = t;
-            }
-        }
+        if (piv != k) swap_rows<INV_THREADS>(A, n2, k, piv, n2);
         __syncthreads();                       // the rows are swapped; rv, ri are read
         const double pv = A[(size_t)k * n2 + k];
         for (int i = k + 1 + tid; i < n; i += INV_THREADS) lcol[i] = A[(size_t)i * n2 + k] / pv;
         __syncthreads();
-        // the trailing block and the right-hand sides: a wave takes every sixteenth row, its lanes the columns
-        for (int j = k + 1 + lane; j < n2; j += 64) {
-            const double pk = A[(size_t)k * n2 + j];
-#pragma unroll 4
-            for (int i = k + 1 + wv; i < n; i += NW) A[(size_t)i * n2 + j] -= lcol[i] * pk;
-        }
+        eliminate<INV_THREADS>(A, n2, k, k + 1, n, k + 1, n2, lcol);      // the trailing block and the right-hand sides
         __syncthreads();
     }
     if (!bad) {
@@ -147,17 +83,13 @@ __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restr
             for (int j = n + tid; j < n2; j += INV_THREADS) A[(size_t)k * n2 + j] /= pv;
             for (int i = tid; i < k; i += INV_THREADS) lcol[i] = A[(size_t)i * n2 + k];
             __syncthreads();
-            for (int j = n + lane; j < n2; j += 64) {
-                const double xk = A[(size_t)k * n2 + j];
-#pragma unroll 4
-                for (int i = wv; i < k; i += NW) A[(size_t)i * n2 + j] -= lcol[i] * xk;
-            }
+            eliminate<INV_THREADS>(A, n2, k, 0, k, n, n2, lcol);
             __syncthreads();
         }
         int nf = 0;
         for (int idx = tid; idx < n * n; idx += INV_THREADS) {
             const int i = idx / n, j = idx - i * n;
-            nf |= !(fabsf((float)A[(size_t)i * n2 + n + j]) <= 3.4028234663852886e38f);       // as it is stored
+            nf |= !finite_as_float(A[(size_t)i * n2 + n + j]);
         }
         if (__syncthreads_or(nf)) bad = -1;
     }
@@ -171,14 +103,15 @@ __global__ __launch_bounds__(INV_THREADS) void k_sr_inverse(const float *__restr
 
 // X[b, c, k] = a'(y) sum_j Z_b[c, j] Ws[j, gene] + l'(y) sum_j (Z_b[c, H + j] v_bj) Wp[j, gene], y = y[b, gene], gene =
 // genes[k]; grid (regulator tiles of 64, row tiles of 64, states); wave w: rows 16 w .. 16 w + 15 of the row tile
-__global__ __launch_bounds__(SR_THREADS) void k_sr_factors(const float *__restrict__ Ws, const float *__restrict__ Wp, int N, int H,
+__global__ __launch_bounds__(ST_THREADS) void k_sr_factors(const float *__restrict__ Ws, const float *__restrict__ Wp, int N, int H,
                                                            const float *__restrict__ y, const float *__restrict__ hid,
                                                            const float *__restrict__ Z, const int *__restrict__ genes, int K,
                                                            float *__restrict__ X)
 {
+    // (not one of the 64 x 64 tile kernels: a wave owns 16 rows x 64 regulators, so no tile_lane)
     const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int b = blockIdx.z, H2 = 2 * H, c0 = blockIdx.y * SR_T + 16 * wv, k0 = blockIdx.x * SR_T;
+    const int b = blockIdx.z, H2 = 2 * H, c0 = blockIdx.y * TILE + 16 * wv, k0 = blockIdx.x * TILE;
     if (c0 >= H2) return;                      // uniform over the wave; the kernel has no barrier
     const int row = c0 + lc;
     const bool rowok = row < H2;
@@ -224,11 +157,11 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_factors(const float *__restri
 
 // one thread per (state, regulator): d = 1 + m sum_c WaT[c, gene] x[c] (c ascending), the column times m (input 0) or
 // divided by d (input 1); a column that is left out -- info[b] != 0, d zero or not finite -- is zeroed, use = 0
-__global__ __launch_bounds__(SR_THREADS) void k_sr_scale(const float *__restrict__ WaT, int N, int H2, const float *__restrict__ m,
+__global__ __launch_bounds__(ST_THREADS) void k_sr_scale(const float *__restrict__ WaT, int N, int H2, const float *__restrict__ m,
                                                          const int *__restrict__ info, const int *__restrict__ genes, int K, int input,
                                                          float *__restrict__ X, float *__restrict__ use)
 {
-    const int b = blockIdx.y, k = blockIdx.x * SR_THREADS + threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x * ST_THREADS + threadIdx.x;
     if (k >= K) return;
     const int gene = genes[k];
     const float mv = m[(size_t)b * N + gene];
@@ -239,8 +172,8 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_scale(const float *__restrict
         float dot = 0.f;
         for (int c = 0; c < H2; ++c) dot = fmaf(WaT[(size_t)c * N + gene], col[(size_t)c * K], dot);
         if (mv != 0.f) d = fmaf(mv, dot, 1.f);
-        else if (!(fabsf(dot) <= 3.4028234663852886e38f)) d = dot;       // a non-finite column of a held regulator
-        ok = fabsf(d) <= 3.4028234663852886e38f && d != 0.f;
+        else if (!finite_as_float(dot)) d = dot;       // a non-finite column of a held regulator
+        ok = finite_as_float(d) && d != 0.f;
     }
     for (int c = 0; c < H2; ++c) {
         const float x = col[(size_t)c * K];
@@ -262,7 +195,7 @@ __device__ __forceinline__ void sr_fetch_x(const sr_args &a, int b, int t, int k
 {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int idx = tid + u * SR_THREADS, rr = idx >> 4, c4 = (idx & 15) * 4, c = t * SR_KC + rr;
+        const int idx = tid + u * ST_THREADS, rr = idx >> 4, c4 = (idx & 15) * 4, c = t * TILE_KC + rr;
         const int left = a.K - (k0 + c4);
         const bool in = c < a.H2 && left > 0;
         v[u] = ld4(a.X + ((size_t)b * a.H2 + (in ? c : 0)) * a.K + (in ? k0 + c4 : 0), in ? left : 0);
@@ -280,22 +213,21 @@ __device__ __forceinline__ void sr_store(float *buf, int tid, const f4 (&v)[2])
 {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-        const int idx = tid + u * SR_THREADS, rr = idx >> 4, c4 = (idx & 15) * 4;
-        *reinterpret_cast<f4 *>(buf + rr * SR_LD + c4) = v[u];      // 16-byte aligned
+        const int idx = tid + u * ST_THREADS, rr = idx >> 4, c4 = (idx & 15) * 4;
+        *reinterpret_cast<f4 *>(buf + rr * TILE_LDK + c4) = v[u];      // 16-byte aligned
     }
 }
 
 template <bool RESIDENT>
-__global__ __launch_bounds__(SR_THREADS) void k_sr_response(sr_args a)
+__global__ __launch_bounds__(ST_THREADS) void k_sr_response(sr_args a)
 {
     extern __shared__ __attribute__((aligned(16))) float sr_lds[];
     float *xbuf = sr_lds;                       // [2][SR_CHUNK]
     float *wbuf = sr_lds + 2 * SR_CHUNK;        // RESIDENT: [T][SR_CHUNK], else [2][SR_CHUNK]
-    const int tid = threadIdx.x, lane = tid & 63, lc = lane & 15, lq = lane >> 4;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int iw = (wv & 1) * 32, jw = (wv >> 1) * 32;
-    const int j0 = blockIdx.x * SR_T, k0 = blockIdx.y * SR_T;
-    const int T = (a.H2 + SR_KC - 1) / SR_KC, steps = a.B * T;
+    const tile_lane L = tile_lanes();
+    const int tid = L.tid, lc = L.lc, lq = L.lq, iw = L.iw, jw = L.jw;
+    const int j0 = blockIdx.x * TILE, k0 = blockIdx.y * TILE;
+    const int T = (a.H2 + TILE_KC - 1) / TILE_KC, steps = a.B * T;
     const bool active = k0 + iw < a.K && j0 + jw < a.N;          // the wave has outputs inside the matrix (uniform)
 
     int gene[2][4];                             // the gene of the lane's rows, -1 outside
@@ -318,14 +250,14 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_response(sr_args a)
     f4 xv[2], wq[2];
     sr_fetch_x(a, 0, 0, k0, tid, xv);
     if (RESIDENT) {
-        for (int idx = tid; idx < T * SR_KC * 16; idx += SR_THREADS) {
+        for (int idx = tid; idx < T * TILE_KC * 16; idx += ST_THREADS) {
             const int rr = idx >> 4, c4 = (idx & 15) * 4;
-            *reinterpret_cast<f4 *>(wbuf + rr * SR_LD + c4) = sr_fetch_w(a, rr, j0, c4);
+            *reinterpret_cast<f4 *>(wbuf + rr * TILE_LDK + c4) = sr_fetch_w(a, rr, j0, c4);
         }
     } else {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            const int idx = tid + u * SR_THREADS;
+            const int idx = tid + u * ST_THREADS;
             wq[u] = sr_fetch_w(a, idx >> 4, j0, (idx & 15) * 4);
         }
         sr_store(wbuf, tid, wq);
@@ -349,8 +281,8 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_response(sr_args a)
             if (!RESIDENT) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
-                    const int idx = tid + u * SR_THREADS;
-                    wq[u] = sr_fetch_w(a, tn * SR_KC + (idx >> 4), j0, (idx & 15) * 4);
+                    const int idx = tid + u * ST_THREADS;
+                    wq[u] = sr_fetch_w(a, tn * TILE_KC + (idx >> 4), j0, (idx & 15) * 4);
                 }
             }
         }
@@ -366,17 +298,9 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_response(sr_args a)
                 for (int r = 0; r < 4; ++r) us[ti][r] = gene[ti][r] >= 0 ? a.use[(size_t)b * a.K + k0 + iw + 16 * ti + 4 * lq + r] : 0.f;
         }
         if (active) {
-            const float *pa = xbuf + cur * SR_CHUNK + lq * SR_LD + iw + lc;
-            const float *pb = (RESIDENT ? wbuf + t * SR_CHUNK : wbuf + cur * SR_CHUNK) + lq * SR_LD + jw + lc;
-#pragma unroll
-            for (int kk = 0; kk < SR_KC / 4; ++kk) {
-                const float a0 = pa[4 * kk * SR_LD], a1 = pa[4 * kk * SR_LD + 16];
-                const float b0 = pb[4 * kk * SR_LD], b1 = pb[4 * kk * SR_LD + 16];
-                dot[0][0] = mfma4(a0, b0, dot[0][0]);
-                dot[0][1] = mfma4(a0, b1, dot[0][1]);
-                dot[1][0] = mfma4(a1, b0, dot[1][0]);
-                dot[1][1] = mfma4(a1, b1, dot[1][1]);
-            }
+            const float *pa = xbuf + cur * SR_CHUNK + lq * TILE_LDK + iw + lc;
+            const float *pb = (RESIDENT ? wbuf + t * SR_CHUNK : wbuf + cur * SR_CHUNK) + lq * TILE_LDK + jw + lc;
+            tile_kloop<1, TILE_LDK>(pa, pb, pb, 2, 2, dot);     // an active wave computes all four tiles
             if (t == T - 1) {                   // the state is complete: fold it into the tile
 #pragma unroll
                 for (int ti = 0; ti < 2; ++ti) {
@@ -423,23 +347,19 @@ __global__ __launch_bounds__(SR_THREADS) void k_sr_response(sr_args a)
         }
 }
 
-bool launched() { return hipGetLastError() == hipSuccess; }
-
-bool sr_shape_ok(const phx_params *p) { return p && p->N >= 1 && p->H >= 1 && p->H <= SR_MAX_H; }
-
 }  // namespace
 
 extern "C" {
 
 size_t phx_steady_inverse_workspace_bytes(int H, int B)
 {
-    if (H < 1 || H > SR_MAX_H || B < 1) return 0;
+    if (!steady_shape_ok(/* N */ 1, H, B)) return 0;
     return (size_t)B * 8 * H * H * sizeof(double);
 }
 
 int phx_steady_inverse(const float *S, int H, int B, float *Z, int *info, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!S || !Z || !info || H < 1 || H > SR_MAX_H || B < 1) return PHX_ERR_BAD_ARG;
+    if (!S || !Z || !info || !steady_shape_ok(/* N */ 1, H, B)) return PHX_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < phx_steady_inverse_workspace_bytes(H, B)) return PHX_ERR_WORKSPACE;
     hipLaunchKernelGGL(k_sr_inverse, dim3((unsigned)B), dim3(INV_THREADS), 0, (hipStream_t)stream, S, 2 * H,
                        static_cast<double *>(workspace), Z, info);
@@ -449,14 +369,15 @@ int phx_steady_inverse(const float *S, int H, int B, float *Z, int *info, void *
 int phx_steady_response_factors(const phx_params *p, const float *y, const float *m, const float *hid, const float *Z,
                                 const int *info, int B, const int *genes, int K, int input, float *X, float *use, void *stream)
 {
-    if (!sr_shape_ok(p) || !p->Ws || !p->Wp || !p->WaT || !y || !m || !hid || !Z || !info || !genes || !X || !use) return PHX_ERR_BAD_ARG;
-    if (B < 1 || B > 65535 || K < 1 || (input != 0 && input != 1)) return PHX_ERR_BAD_ARG;
+    if (!steady_shape_ok(p, B) || !p->Ws || !p->Wp || !p->WaT || !y || !m || !hid || !Z || !info || !genes || !X || !use)
+        return PHX_ERR_BAD_ARG;
+    if (B > 65535 || K < 1 || (input != 0 && input != 1)) return PHX_ERR_BAD_ARG;
     const int N = p->N, H = p->H, H2 = 2 * H;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_sr_factors, dim3((unsigned)((K + SR_T - 1) / SR_T), (unsigned)((H2 + SR_T - 1) / SR_T), (unsigned)B),
-                       dim3(SR_THREADS), 0, st, p->Ws, p->Wp, N, H, y, hid, Z, genes, K, X);
+    hipLaunchKernelGGL(k_sr_factors, dim3((unsigned)((K + TILE - 1) / TILE), (unsigned)((H2 + TILE - 1) / TILE), (unsigned)B),
+                       dim3(ST_THREADS), 0, st, p->Ws, p->Wp, N, H, y, hid, Z, genes, K, X);
     if (!launched()) return PHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(k_sr_scale, dim3((unsigned)((K + SR_THREADS - 1) / SR_THREADS), (unsigned)B), dim3(SR_THREADS), 0, st, p->WaT,
+    hipLaunchKernelGGL(k_sr_scale, dim3((unsigned)((K + ST_THREADS - 1) / ST_THREADS), (unsigned)B), dim3(ST_THREADS), 0, st, p->WaT,
                        N, H2, m, info, genes, K, input, X, use);
     return launched() ? PHX_OK : PHX_ERR_LAUNCH;
 }
@@ -464,9 +385,9 @@ int phx_steady_response_factors(const phx_params *p, const float *y, const float
 int phx_steady_response(const phx_params *p, const float *m, const float *X, const float *use, int B, const int *genes, int K,
                         int input, int mean_abs, float *out, long long ld, void *stream)
 {
-    if (!sr_shape_ok(p) || !p->WaT || !m || !X || !use || !genes || !out) return PHX_ERR_BAD_ARG;
-    if (B < 1 || K < 1 || (input != 0 && input != 1) || ld < p->N) return PHX_ERR_BAD_ARG;
-    const int H2 = 2 * p->H, T = (H2 + SR_KC - 1) / SR_KC;
+    if (!steady_shape_ok(p, B) || !p->WaT || !m || !X || !use || !genes || !out) return PHX_ERR_BAD_ARG;
+    if (K < 1 || (input != 0 && input != 1) || ld < p->N) return PHX_ERR_BAD_ARG;
+    const int H2 = 2 * p->H, T = (H2 + TILE_KC - 1) / TILE_KC;
     if ((long long)B * T > 0x7fffffffLL) return PHX_ERR_BAD_ARG;
     sr_args a;
     a.WaT = p->WaT;
@@ -482,12 +403,12 @@ int phx_steady_response(const phx_params *p, const float *m, const float *X, con
     a.K = K;
     a.input = input;
     a.mean_abs = mean_abs != 0;
-    const dim3 grid((unsigned)((p->N + SR_T - 1) / SR_T), (unsigned)((K + SR_T - 1) / SR_T));
+    const dim3 grid((unsigned)((p->N + TILE - 1) / TILE), (unsigned)((K + TILE - 1) / TILE));
     if (T <= SR_RES_CHUNKS)
-        hipLaunchKernelGGL(k_sr_response<true>, grid, dim3(SR_THREADS), (size_t)(2 + T) * SR_CHUNK * sizeof(float),
+        hipLaunchKernelGGL(k_sr_response<true>, grid, dim3(ST_THREADS), (size_t)(2 + T) * SR_CHUNK * sizeof(float),
                            (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(k_sr_response<false>, grid, dim3(SR_THREADS), (size_t)4 * SR_CHUNK * sizeof(float), (hipStream_t)stream, a);
+        hipLaunchKernelGGL(k_sr_response<false>, grid, dim3(ST_THREADS), (size_t)4 * SR_CHUNK * sizeof(float), (hipStream_t)stream, a);
     return launched() ? PHX_OK : PHX_ERR_LAUNCH;
 }
 
